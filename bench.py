@@ -1,26 +1,39 @@
 """Training-throughput benchmark of the MI355X TransformerVAE step (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5|tiny]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5|tiny] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 `--gpus N` (N > 1) without WORLD_SIZE in the environment: this process launches the N ranks itself (one child
 per GPU with the torchrun environment, as Lightning's Trainer(gpus=N) does for the reference, train.py:63-64, 94),
 never touching the GPU; it exits non-zero at once when fewer than N GPUs are visible. At N > 1 the line also
-carries `scaling_efficiency` against a same-run N=1 rate (all-reduce off, after the timed region) and
-`exposed_comm_ms`: the part of the gradient all-reduce the backward did not hide, per step, max over ranks.
+carries `exposed_comm_ms`: the part of the gradient all-reduce the backward did not hide, per step, max over ranks.
 
 A step = TransformerVAE.training_step (forward) + loss.backward() (engine backward with the bucketed RCCL
 gradient all-reduce overlapped) + on_after_backward (grad norm, KL anneal) + RAdam.step (fused clip +
 update) + LambdaLR.step, on a synthetic batch resident in HBM. Weak scaling: every rank runs the per-GPU
 batch of the config; value = all ranks' tokens / max-over-ranks wall time.
 
-Rank 0 prints ONE JSON line. At N=1 it also carries:
+A plain run sets up, warms up, times the K steps and has rank 0 print ONE JSON line: the throughput (`value`,
+`ms_per_step`), the step's FLOP accounting and
   roofline     — the dominant kernel (the tied vocab-head GEMM, 2*T*d*V flops per launch) timed with HIP
-                 events on its own stream over the timed steps, against the dense bf16 MFMA peak;
-  cpu_baseline — the CPU fp32 oracle (oracle/, pinned to the reference by tests/golden) timed on this
-                 host's cores on a bounded sample of the same workload;
-  parity       — GPU step vs CPU oracle loss / ELBO on the C2 model at batch 2 (same weights, noise).
+                 events on its own stream over the timed steps themselves (no run of its own), against the
+                 dense bf16 MFMA peak.
+The weights (torch seed), the batch and the in-kernel dropout / posterior noise (per-step seeds) are the same in
+every run with the same arguments.
+
+`--dump-outputs DIR`: after the timed steps rank 0 writes what the last timed step handed its caller as
+DIR/<name>.npy (float32): `loss`, the posterior `posterior_mean` / `posterior_scale` of training_step's return value,
+the scalars the step logged (`train_nll`, `train_kl`, `train_mc_mutual_info`, `grad_norm`) and `params`, the f32
+master weights after the step's RAdam update (the whole live arena up to DUMP_PARAMS_MAX elements, else the elements
+at a fixed seeded index sample).
+
+`--full` adds everything that takes a run of its own, after the timed region (and after the dump):
+  cpu_baseline — (N=1) the CPU fp32 oracle (oracle/, pinned to the reference by tests/golden) timed on this
+                 host's cores on a bounded sample of the same workload (`--no-cpu-baseline` drops it);
+  parity       — (N=1) GPU step vs CPU oracle loss / ELBO on the config's model at batch 2 (same weights, noise;
+                 `--no-parity` drops it);
+  scaling_efficiency — (N>1) against a same-run N=1 rate: the K steps re-timed with the all-reduce off.
 """
 import argparse
 import json
@@ -51,6 +64,8 @@ CONFIGS = {
 }
 V, NLAT = 32768, 64
 PEAK_BF16_TFLOPS = 2500.0      # MI355X dense bf16 MFMA (MI355X_MICROARCH.md, chip-level parameters)
+SEED = 7295                    # torch's generator: the random-init weights (and the logged mutual-info draws)
+DUMP_PARAMS_MAX = 4 << 20      # --dump-outputs: f32 master weights written whole up to this many, else sampled (16 MB)
 
 
 def _dec_keys(L, window):
@@ -101,6 +116,24 @@ def step(model, opt, sched, batch):
     sched.step()
     opt.zero_grad()
     return out
+
+
+def dump_outputs(path, model, out):
+    """--dump-outputs: what the last timed step returned and left behind, one float32 .npy per array."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {'loss': out['loss'], 'posterior_mean': out['posterior'].loc, 'posterior_scale': out['posterior'].scale}
+    for k in ('train_nll', 'train_kl', 'train_mc_mutual_info', 'grad_norm'):
+        if torch.is_tensor(model.logged.get(k)):
+            arrays[k] = model.logged[k]
+    flat = model._flat
+    params = flat.master[:flat.n_live]
+    if flat.n_live > DUMP_PARAMS_MAX:
+        idx = np.sort(np.random.default_rng(SEED).integers(0, flat.n_live, size=DUMP_PARAMS_MAX))
+        params = params[torch.from_numpy(idx).to(params.device)]
+    arrays['params'] = params
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), t.detach().to(torch.float32).cpu().numpy())
 
 
 def host_cores():
@@ -271,9 +304,15 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--config', default=None)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-parity', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the last timed step\'s outputs as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the CPU baseline and the oracle parity check (N=1) or the same-run N=1 rate (N>1)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-parity', action='store_true', help='with --full: skip the parity check')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # launcher: this process never touches the GPU; it checks the device count in a child and starts one
@@ -307,6 +346,7 @@ def main():
     cfg_name = args.config or 'c2'
     cfg = CONFIGS[cfg_name]
 
+    torch.manual_seed(SEED)
     model, opt, sched, batch = build(cfg, device)
     if world > 1:
         model.enable_data_parallel()
@@ -325,7 +365,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(model, opt, sched, batch)
+        out = step(model, opt, sched, batch)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -349,9 +389,11 @@ def main():
     fpt = flops_per_token(cfg['layers'], cfg['d'], cfg['L'], window=cfg.get('window', 0))
     fpt_causal = flops_per_token_causal(cfg['layers'], cfg['d'], cfg['L'], window=cfg.get('window', 0))
     loss = model.logged.get('train_nll')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, out)
 
     scaling = None
-    if world > 1:
+    if world > 1 and args.full:
         # same-run N = 1 figure: every rank re-runs the K steps with the data-parallel gradient all-reduce off
         # (model._dp = None is exactly the single-GPU step); after the timed region, so it never enters `value`
         dp, model._dp = model._dp, None
@@ -411,12 +453,12 @@ def main():
         if os.environ.get('SVAE_BENCH_SHARE_GPUS') == '1':
             res['rehearsal'] = (f'NOT a measurement: {world} ranks share {torch.cuda.device_count()} GPU(s), backend '
                                 f'{os.environ.get("SVAE_DIST_BACKEND", "nccl")}')
-        if world == 1 and not args.no_parity:
+        if world == 1 and args.full and not args.no_parity:
             try:
                 res['parity'] = parity_check(cfg, device)
             except Exception as e:  # parity is reported, never allowed to kill the throughput line
                 res['parity'] = {'error': repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(cfg)
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -19,7 +19,7 @@ if [[ $ST == *t* && $rc == 0 ]]; then
   tail -3 "$OUT/pytest_gpu.log"
 fi
 if [[ $ST == *b* && $rc == 0 ]]; then
-  timeout -k 10 300 python -u bench.py --config $CFG > "$OUT/bench.log" 2>&1; rc=$?
+  timeout -k 10 300 python -u bench.py --config $CFG --full > "$OUT/bench.log" 2>&1; rc=$?
   tail -1 "$OUT/bench.log"
 fi
 if [[ $ST == *p* && $rc == 0 ]]; then

@@ -18,7 +18,7 @@ def test_two_rank_bench_rehearsal():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env.update(SVAE_BENCH_SHARE_GPUS='1', SVAE_DIST_BACKEND='gloo')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                        '--config', 'tiny'], capture_output=True, text=True, env=env, timeout=300)
+                        '--config', 'tiny', '--full'], capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout          # rank 0 prints exactly one line
