@@ -457,6 +457,37 @@ int svae_dec_sample(const float* logits, int64_t ldl, int32_t V, int32_t rows, c
                     svae_stream_t stream);
 int svae_dec_advance(int32_t* cur, svae_stream_t stream);
 
+/* ---- latent index: posterior gathering and k-NN search (gather_latents.py:26-31, knn.py:28-50,
+ * math_utils.py:90-101) -------------------------------------------------------------------------------
+ * A corpus is N posteriors q(z|x) = N(mu, scale^2), f32 [N][Z]; Z % 4 == 0, 4 <= Z <= 256, N >= 1 (int32); mu,
+ * scale and inv_var 16-byte aligned. Scores of query q against row i, summed over j:
+ *   L2      sum (mu_q - mu_i)^2                                              smallest first
+ *   COSINE  (mu_q . mu_i) * inv_norm_q * inv_norm_i                          largest first
+ *   KL      KL(N_q || N_i) = (logdet_i - logdet_q)
+ *           + 1/2 sum (scale_q^2 + (mu_q - mu_i)^2) * inv_var_i - Z / 2      smallest first
+ * latent_prepare: the per-row quantities, once: inv_var [N][Z] = 1 / scale^2, logdet [N] = sum log scale,
+ *   inv_norm [N] = 1 / max(|mu|_2, 1e-8) (precise logf, division, sqrtf). Queries are prepared the same way.
+ * latent_scores: out f32 [Q][N]. A metric reads only its own operands (L2: the two mu; COSINE: + the inv_norms; KL:
+ *   q_scale, q_logdet, inv_var, logdet); the others may be NULL.
+ * latent_topk: the best k rows per query (1 <= k <= 64, k <= N), best first: scores f32 [Q][k], indices int32
+ *   [Q][k]. A score is bit-identical to latent_scores' for the same pair; ties go to the lower row index; a NaN
+ *   score ranks after every number. Two launches: a persistent grid (<= SVAE_LATENT_MAX_BLOCKS workgroups, each
+ *   over a contiguous run of rows, queries in tiles of 8 per corpus pass) leaves its best k candidates per query in
+ *   ws, then one workgroup per query merges them. ws: caller-owned, 8-byte aligned, >=
+ *   svae_latent_topk_ws_bytes(Q, k) = Q * SVAE_LATENT_MAX_BLOCKS * k * 8 bytes; its contents need not survive. */
+enum svae_latent_metric { SVAE_LATENT_L2 = 0, SVAE_LATENT_COSINE = 1, SVAE_LATENT_KL = 2 };
+#define SVAE_LATENT_MAX_BLOCKS 1024
+int svae_latent_prepare(const float* mu, const float* scale, float* inv_var, float* logdet, float* inv_norm, int32_t N,
+                        int32_t Z, svae_stream_t stream);
+int svae_latent_scores(int32_t metric, const float* q_mu, const float* q_scale, const float* q_logdet,
+                       const float* q_inv_norm, int32_t Q, const float* mu, const float* inv_var, const float* logdet,
+                       const float* inv_norm, int32_t N, int32_t Z, float* out, svae_stream_t stream);
+int64_t svae_latent_topk_ws_bytes(int32_t Q, int32_t k);
+int svae_latent_topk(int32_t metric, const float* q_mu, const float* q_scale, const float* q_logdet,
+                     const float* q_inv_norm, int32_t Q, const float* mu, const float* inv_var, const float* logdet,
+                     const float* inv_norm, int32_t N, int32_t Z, int32_t k, void* ws, int64_t ws_bytes, float* scores,
+                     int32_t* indices, svae_stream_t stream);
+
 /* library identification: returns a static string (build id, target arch). */
 const char* svae_version(void);
 

@@ -19,6 +19,10 @@ c_fptr = ctypes.c_void_p
 EPI_BF16, EPI_F32, EPI_F32_ACC, EPI_F32_ATOMIC, EPI_GELU, EPI_GELU_BWD, EPI_DROPOUT_RESID, \
     EPI_ROTARY_BF16, EPI_CE_STATS, EPI_CE_PROB, EPI_ROWSCALE_GATHER = range(11)
 
+LATENT_L2, LATENT_COSINE, LATENT_KL = range(3)      # enum svae_latent_metric
+LATENT_METRICS = {'l2': LATENT_L2, 'cosine': LATENT_COSINE, 'kl': LATENT_KL}
+LATENT_MAX_BLOCKS = 1024                             # SVAE_LATENT_MAX_BLOCKS
+
 
 class GemmDesc(ctypes.Structure):
     _fields_ = [
@@ -171,6 +175,12 @@ _SIGS = {
     'svae_dec_advance': [c_void_p, c_void_p],
     'svae_mutual_info': [c_void_p, c_void_p, c_uint64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                          c_void_p],
+    'svae_latent_prepare': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p],
+    'svae_latent_scores': [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_int32, c_int32, c_void_p, c_void_p],
+    'svae_latent_topk_ws_bytes': [c_int32, c_int32],
+    'svae_latent_topk': [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                         c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     'svae_version': [],
 }
 
@@ -184,7 +194,8 @@ def _load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = {'svae_version': ctypes.c_char_p, 'svae_attn_dq_part_elems': c_int64,
-                      'svae_attn_dq_part_elems_w': c_int64, 'svae_attn_fwd_ws_elems': c_int64}.get(name, ctypes.c_int)
+                      'svae_attn_dq_part_elems_w': c_int64, 'svae_attn_fwd_ws_elems': c_int64,
+                      'svae_latent_topk_ws_bytes': c_int64}.get(name, ctypes.c_int)
     return lib
 
 

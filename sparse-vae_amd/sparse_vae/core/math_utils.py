@@ -26,3 +26,18 @@ def marginal_kl(posteriors, num_samples: int = 10, eps=None):
     seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     K.mutual_info(stats, zero, B, Z, seed, out, ws, eps=eps, S=num_samples)   # out = 0 - marginal_kl
     return -out
+
+
+@torch.no_grad()
+def pairwise_gaussian_kl(gaussians):
+    """math_utils.py:90-101: all pairwise KL divergences of a batch of diagonal Gaussians ([B, Z] or [B, 1, Z]) as a
+    square matrix in the reference's [P, Q] convention: entry [p, q] = KL(gaussians[p] || gaussians[q]). Runs on the
+    latent-score kernel (`svae_latent_scores`, the KL metric with the batch as both queries and corpus). No CPU
+    fallback."""
+    mu, scale = gaussians.loc, gaussians.scale
+    if not mu.is_cuda:
+        raise RuntimeError('pairwise_gaussian_kl runs on the MI355X HIP kernels (svae_latent_scores): no CPU fallback')
+    mu = mu.flatten(1).float().contiguous()
+    scale = scale.flatten(1).float().contiguous()
+    inv_var, logdet, inv_norm = K.latent_prepare(mu, scale)
+    return K.latent_scores('kl', (mu, scale, logdet, inv_norm), (mu, inv_var, logdet, inv_norm))

@@ -658,3 +658,78 @@ def dec_sample(logits, V, rows, row_map, out_ids, T, cur, live, end_token, tempe
 
 def dec_advance(cur):
     check(lib.svae_dec_advance(cur.data_ptr(), stream()), 'svae_dec_advance')
+
+
+def _latent_rows(*ts):
+    """The [rows, Z] f32 operands of the latent kernels: contiguous device tensors of one shape."""
+    _dev(*ts)
+    for t in ts:
+        assert t.dtype == f32 and t.dim() == 2 and t.is_contiguous() and t.shape == ts[0].shape
+    return ts[0].shape
+
+
+def latent_prepare(mu, scale, inv_var=None, logdet=None, inv_norm=None):
+    """svae_latent_prepare: from mu, scale f32 [N, Z] the per-row quantities the searches need, computed once:
+    inv_var [N, Z] = 1 / scale^2, logdet [N] = sum log scale, inv_norm [N] = 1 / max(|mu|, 1e-8). Outputs are
+    allocated when not given; returns (inv_var, logdet, inv_norm)."""
+    n, Z = _latent_rows(mu, scale)
+    inv_var = torch.empty_like(mu) if inv_var is None else inv_var
+    logdet = torch.empty(n, dtype=f32, device=mu.device) if logdet is None else logdet
+    inv_norm = torch.empty(n, dtype=f32, device=mu.device) if inv_norm is None else inv_norm
+    _latent_rows(mu, inv_var)
+    for t in (logdet, inv_norm):
+        _dev(t)
+        assert t.dtype == f32 and t.is_contiguous() and t.numel() == n
+    if n:
+        check(lib.svae_latent_prepare(mu.data_ptr(), scale.data_ptr(), inv_var.data_ptr(), logdet.data_ptr(),
+                                      inv_norm.data_ptr(), n, Z, stream()), 'svae_latent_prepare')
+    return inv_var, logdet, inv_norm
+
+
+def _latent_operands(metric, query, corpus):
+    """query = (mu, scale, logdet, inv_norm) [Q, Z] / [Q]; corpus = (mu, inv_var, logdet, inv_norm) [N, Z] / [N]
+    (the outputs of latent_prepare next to their mu); a metric's unused operands may be None."""
+    if isinstance(metric, str):
+        metric = N.LATENT_METRICS[metric]
+    q_mu, q_scale, q_ld, q_in = query
+    c_mu, c_iv, c_ld, c_in = corpus
+    need = {N.LATENT_L2: (), N.LATENT_COSINE: (q_in, c_in), N.LATENT_KL: (q_scale, q_ld, c_iv, c_ld)}[metric]
+    assert all(t is not None for t in need), 'operand missing for this metric'
+    Q, Z = _latent_rows(*[t for t in (q_mu, q_scale) if t is not None])
+    n, Zc = _latent_rows(*[t for t in (c_mu, c_iv) if t is not None])
+    assert Z == Zc and Q >= 1 and n >= 1
+    for t, m in ((q_ld, Q), (q_in, Q), (c_ld, n), (c_in, n)):
+        if t is not None:
+            _dev(t)
+            assert t.dtype == f32 and t.is_contiguous() and t.numel() == m
+    args_q = (q_mu.data_ptr(), ptr(q_scale), ptr(q_ld), ptr(q_in), Q)
+    args_c = (c_mu.data_ptr(), ptr(c_iv), ptr(c_ld), ptr(c_in), n, Z)
+    return metric, args_q, args_c, Q, n
+
+
+def latent_scores(metric, query, corpus, out=None):
+    """svae_latent_scores: the dense f32 [Q, N] score matrix of `metric` ('l2' | 'cosine' | 'kl' or the enum)."""
+    metric, args_q, args_c, Q, n = _latent_operands(metric, query, corpus)
+    if out is None:
+        out = torch.empty(Q, n, dtype=f32, device=query[0].device)
+    _dev(out)
+    assert out.dtype == f32 and out.is_contiguous() and out.shape == (Q, n)
+    check(lib.svae_latent_scores(metric, *args_q, *args_c, out.data_ptr(), stream()), 'svae_latent_scores')
+    return out
+
+
+def latent_topk(metric, query, corpus, k):
+    """svae_latent_topk: the best k corpus rows per query, best first: (scores f32 [Q, k], indices int32 [Q, k]).
+    The candidate workspace is allocated per call (stream-ordered by the caching allocator: nothing shared between
+    calls or streams)."""
+    metric, args_q, args_c, Q, n = _latent_operands(metric, query, corpus)
+    if not 1 <= k <= min(64, n):
+        raise ValueError(f'latent_topk: k = {k} outside 1..min(64, {n} rows)')
+    dev = query[0].device
+    nbytes = lib.svae_latent_topk_ws_bytes(Q, k)
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    scores = torch.empty(Q, k, dtype=f32, device=dev)
+    indices = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    check(lib.svae_latent_topk(metric, *args_q, *args_c, k, ws.data_ptr(), nbytes, scores.data_ptr(),
+                               indices.data_ptr(), stream()), 'svae_latent_topk')
+    return scores, indices

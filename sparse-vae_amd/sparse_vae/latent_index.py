@@ -1,0 +1,200 @@
+"""The posterior latents of a corpus and nearest-neighbour search over them: what the reference does with a trained
+model in gather_latents.py:26-31 (encode every document to a (mean, scale) pair) and knn.py:28-50 (neighbours of an
+article under squared L2 of the means, cosine similarity of the means, and KL between the diagonal Gaussians).
+
+The rows live on the device; every score and the selection run in libsvae's latent kernels (svae_latent_prepare /
+svae_latent_scores / svae_latent_topk, csrc/latent.hip). There is no CPU fallback: an index built from CPU tensors
+keeps its rows, saves and loads, but refuses to search."""
+import numbers
+from typing import Iterable, List, Optional, Sequence
+
+import numpy as np
+import torch
+from torch.distributions.normal import Normal
+
+from . import kernels as K
+
+METRICS = ('l2', 'cosine', 'kl')
+
+
+def _rows(t, Z, name):
+    """[B, Z] or [B, 1, Z] -> f32 [B, Z]."""
+    if t.dim() == 3 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() == 1:
+        t = t[None]
+    if t.dim() != 2 or t.shape[-1] != Z:
+        raise ValueError(f'{name}: expected [B, {Z}] or [B, 1, {Z}], got {tuple(t.shape)}')
+    return t.to(torch.float32)
+
+
+class LatentIndex:
+    def __init__(self, latent_depth: int, device=None):
+        if latent_depth % 4 or not 4 <= latent_depth <= 256:
+            raise ValueError('latent_depth must be a multiple of 4 in 4..256 (svae_latent_* shapes)')
+        self.latent_depth = int(latent_depth)
+        self._device = torch.device(device) if device is not None else None
+        self._n = 0
+        self._cap = 0
+        self._loc = self._scale = self._inv_var = self._logdet = self._inv_norm = None
+        self._titles: List[str] = []
+        self._by_title = None
+
+    # ------------------------------------------------------------------ storage
+    def __len__(self):
+        return self._n
+
+    @property
+    def device(self):
+        return self._device
+
+    @property
+    def loc(self):
+        return self._loc[:self._n] if self._loc is not None else torch.empty(0, self.latent_depth)
+
+    @property
+    def scale(self):
+        return self._scale[:self._n] if self._scale is not None else torch.empty(0, self.latent_depth)
+
+    @property
+    def titles(self):
+        return self._titles
+
+    def _reserve(self, n):
+        if n <= self._cap:
+            return
+        cap = max(n, 2 * self._cap, 1024)        # geometric: a gather loop reallocates O(log N) times
+        Z, dev = self.latent_depth, self._device
+
+        def grown(old, *shape):
+            new = torch.empty(*shape, dtype=torch.float32, device=dev)
+            if old is not None and self._n:
+                new[:self._n].copy_(old[:self._n])
+            return new
+
+        self._loc, self._scale = grown(self._loc, cap, Z), grown(self._scale, cap, Z)
+        self._inv_var = grown(self._inv_var, cap, Z)
+        self._logdet, self._inv_norm = grown(self._logdet, cap), grown(self._inv_norm, cap)
+        self._cap = cap
+
+    def add(self, loc, scale, titles: Optional[Sequence[str]] = None):
+        """Append posteriors: loc, scale [B, Z] or [B, 1, Z]. titles: B strings (default: the running row numbers).
+        On the device the rows' derived quantities are computed here, once (svae_latent_prepare); nothing
+        synchronises."""
+        Z = self.latent_depth
+        loc, scale = _rows(loc, Z, 'loc'), _rows(scale, Z, 'scale')
+        if loc.shape != scale.shape:
+            raise ValueError('loc and scale differ in shape')
+        if self._device is None:
+            self._device = loc.device
+        B, n0 = loc.shape[0], self._n
+        if titles is None:
+            titles = [str(n0 + i) for i in range(B)]
+        titles = [str(t) for t in titles]
+        if len(titles) != B:
+            raise ValueError(f'{len(titles)} titles for {B} rows')
+        if B == 0:
+            return self
+        self._reserve(n0 + B)
+        self._loc[n0:n0 + B].copy_(loc, non_blocking=True)
+        self._scale[n0:n0 + B].copy_(scale, non_blocking=True)
+        if self._device.type == 'cuda':
+            K.latent_prepare(self._loc[n0:n0 + B], self._scale[n0:n0 + B], self._inv_var[n0:n0 + B],
+                             self._logdet[n0:n0 + B], self._inv_norm[n0:n0 + B])
+        self._titles.extend(titles)
+        self._by_title = None
+        self._n = n0 + B
+        return self
+
+    def row_of(self, title: str) -> Optional[int]:
+        """Row of the first posterior with this title, or None."""
+        if self._by_title is None:
+            self._by_title = {}
+            for i, t in enumerate(self._titles):
+                self._by_title.setdefault(t, i)
+        return self._by_title.get(title)
+
+    # ------------------------------------------------------------------ search
+    def _corpus(self):
+        if self._n == 0:
+            raise ValueError('the index is empty')
+        if self._device.type != 'cuda':
+            raise RuntimeError('LatentIndex searches run on the MI355X HIP kernels (svae_latent_*): move the index to '
+                               'a GPU (LatentIndex.load(path, device)). There is no CPU fallback.')
+        n = self._n
+        return self._loc[:n], self._inv_var[:n], self._logdet[:n], self._inv_norm[:n]
+
+    def _query(self, query):
+        """-> (mu, scale, logdet, inv_norm) of the queries, prepared like the rows."""
+        Z = self.latent_depth
+        if isinstance(query, numbers.Integral) or (torch.is_tensor(query) and not query.is_floating_point()):
+            n = self._n
+            if torch.is_tensor(query) and query.is_cuda:
+                # not read back (that would synchronise): rows outside 0..n-1 are clamped to the nearest valid row
+                # instead of reaching a device-side index assert
+                idx = query.to(self._device, torch.int64).reshape(-1).clamp(0, n - 1)
+            else:
+                idx = torch.as_tensor(query if torch.is_tensor(query) else int(query), dtype=torch.int64).reshape(-1)
+                if idx.numel() and not (0 <= int(idx.min()) and int(idx.max()) < n):
+                    raise IndexError(f'row index outside the index (0..{n - 1}): {idx.tolist()[:8]}')
+                idx = idx.to(self._device)
+            return (self._loc[:n][idx].contiguous(), self._scale[:n][idx].contiguous(),
+                    self._logdet[:n][idx].contiguous(), self._inv_norm[:n][idx].contiguous())
+        if isinstance(query, Normal):
+            loc, scale = query.loc, query.scale
+        else:
+            loc, scale = query
+        loc = _rows(loc, Z, 'query loc').to(self._device).contiguous()
+        scale = _rows(scale, Z, 'query scale').to(self._device).contiguous()
+        _, logdet, inv_norm = K.latent_prepare(loc, scale)
+        return loc, scale, logdet, inv_norm
+
+    def search(self, query, k: int = 10, metric: str = 'l2'):
+        """The k nearest rows per query, best first: (scores f32 [Q, k], indices int64 [Q, k]) on the device. query:
+        a Normal, a (loc, scale) pair, or an int / int tensor of rows of this index (a row is its own first hit, as
+        in knn.py). An int or a CPU int tensor outside 0..len-1 raises IndexError; a device int tensor is not read
+        back, its rows are clamped into that range. metric: 'l2' (squared distance of the means, smallest first), 'cosine' (similarity of the
+        means, largest first), 'kl' (KL(query || row), smallest first)."""
+        if metric not in METRICS:
+            raise ValueError(f"metric must be one of {METRICS}, got '{metric}'")
+        corpus = self._corpus()
+        scores, indices = K.latent_topk(metric, self._query(query), corpus, int(k))
+        return scores, indices.to(torch.int64)
+
+    def scores(self, query, metric: str = 'l2'):
+        """The dense [Q, N] score matrix of `metric` (svae_latent_scores)."""
+        if metric not in METRICS:
+            raise ValueError(f"metric must be one of {METRICS}, got '{metric}'")
+        corpus = self._corpus()
+        return K.latent_scores(metric, self._query(query), corpus)
+
+    # ------------------------------------------------------------------ persistence
+    def save(self, path):
+        """One .npz: loc, scale, titles. The derived rows are not stored (load recomputes them)."""
+        with open(path, 'wb') as f:
+            np.savez(f, loc=self.loc.detach().cpu().numpy(), scale=self.scale.detach().cpu().numpy(),
+                     titles=np.asarray(self._titles, dtype=np.str_))
+
+    @classmethod
+    def load(cls, path, device=None):
+        with np.load(path, allow_pickle=False) as z:
+            loc, scale, titles = z['loc'], z['scale'], [str(t) for t in z['titles']]
+        index = cls(loc.shape[1], device=device)
+        if len(loc):
+            dev = index._device if index._device is not None else torch.device('cpu')
+            index.add(torch.from_numpy(loc).to(dev), torch.from_numpy(scale).to(dev), titles)
+        return index
+
+
+@torch.no_grad()
+def gather_latents(model, batches: Iterable, titles_key: str = 'title') -> LatentIndex:
+    """gather_latents.py:26-31: q(z|x) of every batch through model.encode (encoder only), appended on the device
+    with no per-batch host synchronisation. Batches without `titles_key` get their running row numbers as titles."""
+    index = LatentIndex(model.hparams.latent_depth, device=model.device)
+    for batch in batches:
+        q = model.encode(batch)
+        titles = batch.get(titles_key) if hasattr(batch, 'get') else None
+        if titles is not None:
+            titles = [''.join(t) if not isinstance(t, str) else t for t in titles]
+        index.add(q.loc, q.scale, titles)
+    return index

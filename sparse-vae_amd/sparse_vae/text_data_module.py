@@ -222,6 +222,8 @@ class TextDataModule:
         }
         if 'label' in inputs[0]:
             batch['label'] = torch.tensor([int(x['label']) for x in inputs])
+        if 'title' in inputs[0]:
+            batch['title'] = [str(x['title']) for x in inputs]     # gather_latents.py:31 reads the batch's titles
         return batch
 
     def pad_pack(self, batch: List[torch.Tensor], pad_value: int = 0) -> torch.Tensor:

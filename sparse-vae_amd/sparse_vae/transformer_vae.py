@@ -486,3 +486,16 @@ class TransformerVAE(ContinuousVAEHooks, LanguageModel):
         self.training_step(batch, stage='predict', dropout=0.0)
         mu, logvar = self._last['mu'], self._last['logvar']
         return Normal(mu.view(-1, 1, mu.shape[-1]).clone(), logvar.exp().sqrt().view(-1, 1, mu.shape[-1]))
+
+    @torch.no_grad()
+    def encode(self, batch) -> Normal:
+        """q(z|x) for a batch through the encoder alone (engine.posterior): what gather_latents.py:26-31 and
+        vae-console.py need from a trained model. Same batch dicts as `predict` (PaddedTensor or plain ids), same
+        encoder kernels at dropout 0, so loc and scale [B, 1, latent] equal predict's; the decoder, the vocabulary
+        head, the CE and the mutual-information kernels do not run."""
+        eng = self._require_engine()
+        ids, pad, _ = self._batch_inputs(batch)
+        Z = self.hparams.latent_depth
+        stats = eng.posterior(ids, pad if pad is not None else False)
+        return Normal(stats[:, :Z].reshape(-1, 1, Z).clone(), stats[:, Z:].exp().sqrt().reshape(-1, 1, Z),
+                      validate_args=False)
