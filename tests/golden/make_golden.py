@@ -2,7 +2,7 @@
 
 Run in the survey/build container only (the GPU box has no /root/reference):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py            (or with one of: <config names> | sparse | ce | eval | sampler)
 
 Writes tests/golden/<name>.npz (+ reference_keys.json). Weights are never stored: both the reference and
 every consumer regenerate them from `oracle.params.init_params(hp, seed)` (portable splitmix64 normals).
@@ -334,11 +334,97 @@ def ce_vectors(sv):
     print(f'ce_chunked: nll={nll.item():.6f} weighted={wnll.item():.6f} single-chunk mean={single.item():.6f}')
 
 
+# (top_k, top_p, temperature); (40, 0.7, 0.8) is the branch that re-binds token_ids to the sort permutation
+SAMPLER_CONFIGS = [(0, 0.9, 0.8), (0, 0.5, 1.0), (40, 1.0, 0.8), (40, 0.7, 0.8), (0, 1.0, 1.3)]
+SAMPLER_V = 2000
+SAMPLER_ROW_SCALES = (1.0, 2.0, 3.0, 5.0)    # flat to peaked rows
+
+
+SAMPLER_RANK_CONFIG = 3                      # its index in SAMPLER_CONFIGS
+SAMPLER_WIDE_V = 4096                        # top_k * 64 <= V: ATen's CPU topk(sorted=False) comes back sorted
+
+
+def sampler_vectors(sv):
+    """GenerationState.process_logits (generation.py:30-77) as a map column -> emitted id. `Tensor.multinomial`
+    is patched: a first call records the `probs` the reference would sample from; then every non-zero column is
+    forced once (one batch row per column, all rows holding the same logits) and the id process_logits writes to
+    output_ids is recorded. Stored per config: the (emitted id, probability) pairs of the four logits rows,
+    concatenated in ascending id order, with the row offsets, and the forced columns in the same order; the
+    probabilities are the reference's f32 `probs` as sampled from (masked, not renormalised).
+
+    With top_k > 0 and top_p < 1 the reference emits `sort_permutation[column]`, the sampled element's position in
+    the output of `logits.topk(k, sorted=False)`, whose order torch leaves unspecified. ATen's CPU kernel returns
+    it sorted (partial_sort) when k * 64 <= V, so the emitted id is then the descending rank (= the column), and
+    in nth_element order otherwise. V = 2000, k = 40 is the second kind: those rows record what this torch build
+    emits, which nothing else can restate. The same config is therefore also recorded on two rows of V = 4096
+    (`logits_wide`, keys with the suffix `w`), where the emitted id is the rank; that is asserted here."""
+    GS = sys.modules['sparse_vae.core.generation'].GenerationState
+
+    def rows(V, tag, scales):
+        lg = np.stack([s * portable_normal(V, f'sampler_logits{tag}{r}', 77)
+                       for r, s in enumerate(scales)]).astype(np.float32)
+        top = -np.sort(-lg, axis=-1)[:, :42]
+        assert (np.diff(top, axis=-1) < 0).all(), 'ties among the top 42 logits of a row'
+        return lg
+
+    logits = rows(SAMPLER_V, '', SAMPLER_ROW_SCALES)
+    wide = rows(SAMPLER_WIDE_V, 'w', SAMPLER_ROW_SCALES[:2])
+    rec = {'logits': logits, 'logits_wide': wide, 'configs': np.asarray(SAMPLER_CONFIGS, dtype=np.float64)}
+    orig = torch.Tensor.multinomial
+    forced = {}
+
+    def multinomial(self, num_samples, *a, **k):
+        forced['probs'] = self.detach().clone()
+        return forced['cols'].view(-1, 1).clone()
+
+    def record(lg, top_k, top_p, temp):
+        ids, probs, columns, offs = [], [], [], [0]
+        for r in range(lg.shape[0]):
+            row = torch.from_numpy(lg[r:r + 1])
+
+            def run(cols):
+                st = GS(4, cols.numel(), 1, -1, torch.device('cpu'), top_k=top_k, top_p=top_p, temperature=temp,
+                        repetition_penalty=1.0)
+                forced['cols'] = cols
+                st.process_logits(row.expand(cols.numel(), -1).clone())
+                return st.output_ids[:, 1].clone()
+
+            run(torch.zeros(1, dtype=torch.long))
+            p = forced['probs'][0]
+            cols = p.nonzero().flatten()
+            out = run(cols)
+            assert torch.equal(forced['probs'], p.expand(cols.numel(), -1)), 'rows of one batch differ'
+            assert out.unique().numel() == out.numel()
+            order = out.argsort()
+            ids.append(out[order].numpy().astype(np.int32))
+            probs.append(p[cols][order].numpy().astype(np.float32))
+            columns.append(cols[order].numpy().astype(np.int32))
+            offs.append(offs[-1] + cols.numel())
+        return (np.concatenate(ids), np.concatenate(probs), np.concatenate(columns),
+                np.asarray(offs, dtype=np.int64))
+
+    torch.Tensor.multinomial = multinomial
+    try:
+        for c, cfg in enumerate(SAMPLER_CONFIGS):
+            rec[f'ids{c}'], rec[f'probs{c}'], rec[f'cols{c}'], rec[f'offsets{c}'] = record(logits, *cfg)
+            print(f'gen_sampler config {c} {cfg}: support sizes {np.diff(rec[f"offsets{c}"]).tolist()}')
+        c = SAMPLER_RANK_CONFIG
+        rec[f'ids{c}w'], rec[f'probs{c}w'], rec[f'cols{c}w'], rec[f'offsets{c}w'] = record(wide, *SAMPLER_CONFIGS[c])
+        assert np.array_equal(rec[f'ids{c}w'], rec[f'cols{c}w']), 'topk(sorted=False) was not sorted at the wide V'
+        print(f'gen_sampler config {c} at V {SAMPLER_WIDE_V}: support sizes {np.diff(rec[f"offsets{c}w"]).tolist()}')
+    finally:
+        torch.Tensor.multinomial = orig
+    np.savez_compressed(os.path.join(HERE, 'gen_sampler.npz'), **rec)
+
+
 def main():
     torch.set_num_threads(min(8, os.cpu_count()))
     sv = ref_stubs.import_reference()
     keys = {}
     only = sys.argv[1:]
+    if only == ['sampler']:
+        sampler_vectors(sv)
+        return
     if only == ['sparse']:
         sparse_vectors(sv)
         return
@@ -362,6 +448,7 @@ def main():
         json.dump(keys, f, indent=0)
     if not only:
         op_vectors(sv)
+        sampler_vectors(sv)
 
 
 if __name__ == '__main__':
