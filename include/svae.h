@@ -105,6 +105,26 @@ int svae_gemm(const svae_gemm_desc* d, svae_stream_t stream);
  * splits); the results equal two svae_gemm calls with the same descs. */
 int svae_gemm_pair(const svae_gemm_desc* d0, const svae_gemm_desc* d1, svae_stream_t stream);
 
+/* n weight-gradient GEMMs as one grouped pass (engine.backward defers every layer's nn.Linear weight gradients,
+ * transformer_layer.py:56-61 and attention.py:51-105 under loss.backward(), to one call: the chip is filled across
+ * layers instead of across K). d[0..n): each as for svae_gemm with a_t = b_t = 1, batch 1, and either splits == 1
+ * with epi SVAE_EPI_F32_ACC (C += the product, one accumulation chain over K) or splits >= 1 with epi
+ * SVAE_EPI_F32_ATOMIC and a slab workspace of its own in aux (as for svae_gemm_pair); a_rowsum as for svae_gemm. The
+ * unsplit GEMMs run as one launch of 256 x 256 tiles, the split ones as a second, and one launch adds every slab
+ * into its C in split order; the results equal n svae_gemm calls with the same descs.
+ *   max_blocks: 0 = one block per compute unit; then the unsplit GEMMs together must not have more tiles than that
+ *     (a second round of whole-K tiles would cost a full tile time: SVAE_EINVAL -- give the rest a split count).
+ *     > 0 (<= SVAE_GROUP_MAX_BLOCKS): at most that many blocks per launch, which then walk several tiles each.
+ *   table / table_host: the parameter table the kernels read, in device memory (16-byte aligned), and the caller's
+ *     host copy of it, both of table_bytes >= svae_gemm_group_table_bytes(n) bytes and owned by the caller;
+ *     table_host zeroed before its first use. The device table is written (a copy on `stream`, waited for) only
+ *     when its contents differ from table_host, i.e. not in a step that repeats the previous step's addresses. */
+#define SVAE_GROUP_MAX 256
+#define SVAE_GROUP_MAX_BLOCKS 1024
+int64_t svae_gemm_group_table_bytes(int32_t n);
+int svae_gemm_group(const svae_gemm_desc* d, int32_t n, int32_t max_blocks, void* table, void* table_host,
+                    int64_t table_bytes, svae_stream_t stream);
+
 /* ---- LayerNorm ---------------------------------------------------------------------------------
  * nn.LayerNorm(d, eps=1e-5) forward/backward: transformer_layer.py:23-24,39-40,47,52,56;
  * transformer_language_model.py:59. x_dtype: 0 = f32 input, 1 = bf16 input. y is bf16.

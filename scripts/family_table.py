@@ -10,7 +10,8 @@ import sys
 FAMILIES = [
     ('vocab head GEMMs (fwd CE_PROB, dX, k-weighted dW)', 'MFMA',
      r'gemm256_kernel<(false, false, (9|10)|true, true, (64|66))>'),
-    ('weight-gradient GEMMs (paired split-K) + slab reduce', 'MFMA', r'gemm256_pair_kernel|gemm256_kernel<true, true, 67>|slab_reduce'),
+    ('weight-gradient GEMMs (grouped / paired split-K) + slab reduce', 'MFMA',
+     r'gemm256_group_kernel|gemm256_pair_kernel|gemm256_kernel<true, true, 67>|slab_reduce'),
     ('forward / dX GEMMs (fused epilogues)', 'MFMA', r'gemm256_kernel|gemm_glds_kernel|gemm_kernel|gemm_skinny'),
     ('attention backward (+ dQ reduce, delta, [CLS] split)', 'MFMA / sync',
      r'attn_bwd|attn_dq_reduce|attn_delta|attn_cls'),

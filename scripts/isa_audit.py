@@ -39,6 +39,10 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-munsafe-fp-atomics', '--cuda-device-only', '-S']
 NO_NANS = ('attention.hip', 'gemm.hip')          # the Makefile's -fno-honor-nans files
 
+# kernels that must not spill at all (a spill reload's compiler vmcnt(0) drains the hand-counted DMA ring): the grouped
+# weight-gradient launch, unsplit (epilogue 2, f32 accumulate) and split-K slab (67). A spill there counts as a hazard.
+NO_SPILL = ('gemm256_group_kernelILi2E', 'gemm256_group_kernelILi67E')
+
 VALU_SGPR_DST0 = re.compile(r'^v_(readfirstlane|readlane|cmpx?_\w+_e64)')
 VALU_SGPR_DST1 = re.compile(r'^v_(add_co|sub_co|subrev_co|addc_co|subb_co|subbrev_co|mad_u64_u32|mad_i64_i32|'
                             r'div_scale)')
@@ -251,6 +255,8 @@ def main():
         for name, body in parse(s):
             issues, scratch = audit_kernel(name, body)
             vsp, ssp, vg = meta.get(name, (-1, -1, -1))
+            if any(k in name for k in NO_SPILL) and (vsp != 0 or scratch):
+                issues.append(('SPILL', 0, f'{vsp} spilled VGPRs, {scratch} scratch instructions'))
             ndma = sum(1 for k, t in body if k == 'ins' and t.endswith(' lds'))
             nasync = sum(1 for k, t in body if k == 'ins' and re.match(r'buffer_load_dword(x[234])?$', t.split()[0]) and
                          not t.endswith('lds') and re.search(r'\boffen( offset:\d+)?$', t))
@@ -264,6 +270,11 @@ def main():
                       f'{scratch} scratch instructions ({inloop} inside loops, {inner} in an MFMA loop)')
             for kind, i, text in issues:
                 print(f'    {kind} @{i}: {text}')
+    if any(os.path.basename(f) == 'gemm.hip' for f in files):
+        for k in NO_SPILL:
+            if sum(k in name for name in report) != 1:
+                print(f'    SPILL: no kernel (or several) named {k} in gemm.hip')
+                bad += 1
     print(f'{bad} hazard(s)')
     if args.json:
         import json

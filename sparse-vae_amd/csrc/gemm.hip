@@ -11,7 +11,9 @@
 #include "common.h"
 #include "../../include/svae.h"
 #include <stdlib.h>
+#include <string.h>
 #include <algorithm>
+#include <vector>
 
 using namespace svae;
 
@@ -1225,7 +1227,7 @@ constexpr int g3_epi_vmem_ops() {
 // The gemm256 block program over the tiles of one GEMM: block `blk` of `nwg` blocks working on p (the plain kernel
 // passes blockIdx.x / gridDim.x; the paired kernel gives each GEMM its own range of blocks).
 template <bool AT, bool BT, int EPI>
-__device__ __forceinline__ void gemm256_run(const GP& p, int blk, int nwg) {
+__device__ __forceinline__ void gemm256_run(const GP& p, int blk, int nwg, bool remap = true) {
   // 2 ring stages + a side area: the epilogue's per-tile bias (256 f32), CE labels (256 i32) and CE row statistics
   // ([256 rows][4 column waves][max, sum]); one array
   static_assert(g3_epi_vmem_ops<EPI>() >= G3_EPI_STORES, "the relaxed first wait would not cover the prefetch DMA");
@@ -1249,9 +1251,10 @@ __device__ __forceinline__ void gemm256_run(const GP& p, int blk, int nwg) {
   const int wr = wave >> 2, wc = wave & 3;
   // XCD-aware bijective remap of the block id; block b then walks tiles b, b + G, b + 2G, ... (G = nwg):
   // with G = 256 every XCD runs one contiguous N-fastest range of tiles at a time. (blk % 8 is the XCD: the paired
-  // kernel's block ranges start at multiples of 8.)
+  // kernel's block ranges start at multiples of 8; the grouped kernel's host-built block map has placed its blocks
+  // already: remap = false.)
   int bid = blk;
-  if (nwg >= 16) {
+  if (remap && nwg >= 16) {
     const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
@@ -1535,6 +1538,41 @@ __global__ __launch_bounds__(512, 1) void gemm256_pair_kernel(GP2 q) {
   gemm256_run<AT, BT, EPI>(q.p[sel], sel ? b - q.nb0 : b, sel ? (int)gridDim.x - q.nb0 : q.nb0);
 }
 
+// N independent weight-gradient GEMMs in one launch (svae_gemm_group: every layer's dW GEMMs of a backward, so the
+// chip is filled across layers instead of across K). The parameter sets live in a device-memory table (N of them do
+// not fit the kernel arguments); a block reads its map entry (GEMM, block index within the GEMM, blocks of that GEMM)
+// and that GEMM's parameters with scalar loads (a uniform address in the constant address space), then runs the same
+// block program as the plain and the paired kernel. The host built the map: which hardware block (id % 8 = XCD) works
+// on which GEMM, so the tiles of one GEMM march through K together on one L2.
+struct alignas(16) GPSlot {
+  GP p;
+};
+struct alignas(16) GMap {
+  int gemm, blk, nblk, pad;   // gemm < 0: an unused slot of the last XCD row
+};
+
+template <class T>
+__device__ __forceinline__ T load_uniform(const T* src) {
+  static_assert(sizeof(T) % 4 == 0, "whole dwords");
+  typedef const unsigned __attribute__((address_space(4))) * cu32p;
+  struct W {
+    unsigned w[sizeof(T) / 4];
+  } r;
+  const cu32p c = (cu32p)(uintptr_t)src;
+#pragma unroll
+  for (unsigned i = 0; i < sizeof(T) / 4; ++i) r.w[i] = c[i];
+  return __builtin_bit_cast(T, r);
+}
+
+template <int EPI>
+__global__ __launch_bounds__(512, 1) void gemm256_group_kernel(const GPSlot* __restrict__ tab,
+                                                               const GMap* __restrict__ map) {
+  const GMap e = load_uniform(map + blockIdx.x);
+  if (e.gemm < 0) return;
+  const GP p = load_uniform(&tab[e.gemm].p);
+  gemm256_run<true, true, EPI>(p, e.blk, e.nblk, false);
+}
+
 // ===================================================================================================
 // gemm_skinny: M <= 64 rows (the encoder bottleneck layer, q(z|x), the z projections: one row per sequence).
 // A 128-row tile leaves such a GEMM to a handful of blocks that walk all of K serially (a 64 x 512 x 2048 dropout +
@@ -1658,6 +1696,16 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(SlabRed r) { slab_redu
 __global__ __launch_bounds__(256) void slab_reduce2_kernel(SlabRed r0, SlabRed r1, int nb0) {
   if ((int)blockIdx.x < nb0) slab_reduce_range(r0, blockIdx.x, nb0);
   else slab_reduce_range(r1, blockIdx.x - nb0, (int)gridDim.x - nb0);
+}
+// the slab reductions of a grouped dW launch (a list in device memory): every block takes its stride of each entry
+struct alignas(16) SlabRedSlot {
+  SlabRed r;
+};
+__global__ __launch_bounds__(256) void slab_reduce_list_kernel(const SlabRedSlot* __restrict__ list, int n) {
+  for (int e = 0; e < n; ++e) {
+    const SlabRed r = load_uniform(&list[e].r);
+    slab_reduce_range(r, blockIdx.x, gridDim.x);
+  }
 }
 
 }  // namespace
@@ -2009,6 +2057,171 @@ SVAE_EXPORT int svae_gemm_pair(const svae_gemm_desc* d0, const svae_gemm_desc* d
   const long long b0 = slab_blocks(d0), b1 = slab_blocks(d1);
   hipLaunchKernelGGL(slab_reduce2_kernel, dim3((unsigned)(b0 + b1)), dim3(256), 0, s, slab_red(d0), slab_red(d1), (int)b0);
   SVAE_LAUNCH_CHECK();
+  return SVAE_OK;
+}
+
+// ---- svae_gemm_group: N weight-gradient GEMMs as one launch per class (unsplit / split-K slab) + one slab reduction
+namespace {
+
+struct GroupHeader {   // first bytes of the table: what the rest was built for
+  unsigned long long bytes, dev;
+  int n, grid_a, grid_b, nred;
+};
+static_assert(sizeof(GroupHeader) == 32, "table header");
+
+constexpr long long group_align(long long x) { return (x + 15) / 16 * 16; }
+
+// Blocks -> hardware block ids. Block id b runs on XCD b % 8, and a launch of <= one block per CU is resident at
+// once, so XCD x owns the slots x, x + 8, x + 16, ... Each GEMM's nb[g] blocks go to the first XCD that still has
+// room for all of them, largest GEMM first (at C2 the 16- and the 12 + 4-tile GEMMs of a layer pack an XCD's 32
+// slots exactly); a GEMM that fits nowhere whole takes free slots in XCD order. Speed only: any map that names
+// every (gemm, blk) once is correct.
+void place_blocks(const std::vector<int>& gemm, const std::vector<int>& nb, std::vector<GMap>& map) {
+  long long total = 0;
+  for (int x : nb) total += x;
+  const int grid = (int)((total + 7) / 8 * 8), per = grid / 8;
+  map.assign(grid, GMap{-1, 0, 0, 0});
+  int used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::vector<int> order(nb.size());
+  for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return nb[a] > nb[b]; });
+  for (int i : order) {
+    int x = 0;
+    while (x < 8 && per - used[x] < nb[i]) ++x;
+    int blk = 0;
+    for (int y = x < 8 ? x : 0; blk < nb[i] && y < 8; ++y)
+      while (blk < nb[i] && used[y] < per) map[(size_t)used[y]++ * 8 + y] = GMap{gemm[i], blk++, nb[i], 0};
+  }
+}
+
+int device_cus() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      n = 256;
+    return n > 0 ? n : 256;
+  }();
+  return ncu;
+}
+
+}  // namespace
+
+SVAE_EXPORT int64_t svae_gemm_group_table_bytes(int32_t n) {
+  if (n <= 0 || n > SVAE_GROUP_MAX) return 0;
+  return (int64_t)(sizeof(GroupHeader) + n * (sizeof(GPSlot) + sizeof(SlabRedSlot)) +
+                   2 * (SVAE_GROUP_MAX_BLOCKS + 8) * sizeof(GMap));
+}
+
+SVAE_EXPORT int svae_gemm_group(const svae_gemm_desc* d, int32_t n, int32_t max_blocks, void* table, void* table_host,
+                                int64_t table_bytes, svae_stream_t stream) {
+  if (!d || n <= 0 || n > SVAE_GROUP_MAX || max_blocks < 0 || max_blocks > SVAE_GROUP_MAX_BLOCKS || !table ||
+      !table_host || ((uintptr_t)table & 15) || table_bytes < svae_gemm_group_table_bytes(n))
+    return SVAE_EINVAL;
+  const int cap = max_blocks ? max_blocks : std::min(device_cus(), (int)SVAE_GROUP_MAX_BLOCKS);
+  std::vector<GPSlot> gp(n);
+  std::vector<SlabRedSlot> red;
+  std::vector<int> idx[2], units[2], nb[2];   // class 0: unsplit (F32_ACC), class 1: split-K slabs
+  std::vector<double> work[2];
+  long long red_elems = 0;
+  for (int i = 0; i < n; ++i) {
+    const svae_gemm_desc* di = d + i;
+    if (const int rc = validate_desc(di)) return rc;
+    const bool split = di->epi == SVAE_EPI_F32_ATOMIC;
+    // the weight-gradient shape only (as svae_gemm_pair), unsplit into C or K slices into a slab
+    if (!di->a_t || !di->b_t || di->batch != 1 || di->k_weight || di->bias || di->resid ||
+        (!split && (di->epi != SVAE_EPI_F32_ACC || di->splits != 1)) || (split && (!di->aux || ((uintptr_t)di->aux & 15))))
+      return SVAE_EINVAL;
+    GP& p = gp[i].p;
+    memset(&gp[i], 0, sizeof(GPSlot));
+    fill_gp(di, p);
+    p.bias = nullptr; p.resid = nullptr; p.aux = nullptr;
+    if (split) {
+      p.C = di->aux; p.ldc = di->N; p.sC = 0; p.slab = (long long)di->M * di->N;
+      p.epi = G3_EPI_SLAB;
+    }
+    const int kc3 = (di->K + di->splits - 1) / di->splits;
+    p.kchunk = (kc3 + 63) / 64 * 64;
+    p.tn2 = (di->N + 255) / 256;
+    p.tm2 = (di->M + 255) / 256;
+    p.group = 0;
+    const long long u = (long long)p.tn2 * p.tm2 * di->splits;
+    if (u > (1 << 24)) return SVAE_EINVAL;
+    p.total3 = (int)u;
+    p.relaxed = 1;
+    // (the long unsplit K loops stagger their DMA issue as svae_gemm's do; the short split slices as the pairs, not)
+    p.dma_stagger = split ? 0 : 1;
+    const int c = split ? 1 : 0;
+    idx[c].push_back(i);
+    units[c].push_back((int)u);
+    work[c].push_back((double)u * ((p.kchunk + 63) / 64 + 8));   // K-tiles + an epilogue's worth per unit
+    if (split) {
+      SlabRedSlot s;
+      memset(&s, 0, sizeof(s));
+      s.r = slab_red(di);
+      red.push_back(s);
+      red_elems += (long long)di->M * (di->N / 4);
+    }
+  }
+  std::vector<GMap> map[2];
+  for (int c = 0; c < 2; ++c) {
+    const int m = (int)idx[c].size();
+    if (!m) continue;
+    long long total = 0;
+    double wsum = 0;
+    for (int k = 0; k < m; ++k) total += units[c][k], wsum += work[c][k];
+    // an unsplit tile walks all of K: a second round of them would cost a whole tile time more. The caller's
+    // schedule gives what one round does not hold a split count; only an explicit max_blocks lets blocks walk units.
+    if (c == 0 && !max_blocks && total > cap) return SVAE_EINVAL;
+    if (cap < m) return SVAE_EINVAL;
+    nb[c].resize(m);
+    if (total <= cap) nb[c] = units[c];
+    else   // blocks walk several units of their GEMM: one block each, the rest in proportion to the work
+      for (int k = 0; k < m; ++k)
+        nb[c][k] = std::min(units[c][k], 1 + (int)((cap - m) * (work[c][k] / wsum)));
+    place_blocks(idx[c], nb[c], map[c]);
+  }
+  // the table: header | parameter sets | block maps | slab reductions
+  const long long o_gp = sizeof(GroupHeader), o_ma = o_gp + (long long)n * sizeof(GPSlot);
+  const long long o_mb = o_ma + (long long)map[0].size() * sizeof(GMap);
+  const long long o_red = o_mb + (long long)map[1].size() * sizeof(GMap);
+  const long long bytes = o_red + (long long)red.size() * sizeof(SlabRedSlot);
+  if (bytes > table_bytes) return SVAE_EINVAL;
+  std::vector<char> img((size_t)bytes, 0);
+  const GroupHeader h{(unsigned long long)bytes, (unsigned long long)(uintptr_t)table, n, (int)map[0].size(),
+                      (int)map[1].size(), (int)red.size()};
+  memcpy(img.data(), &h, sizeof(h));
+  memcpy(img.data() + o_gp, gp.data(), (size_t)n * sizeof(GPSlot));
+  if (!map[0].empty()) memcpy(img.data() + o_ma, map[0].data(), map[0].size() * sizeof(GMap));
+  if (!map[1].empty()) memcpy(img.data() + o_mb, map[1].data(), map[1].size() * sizeof(GMap));
+  if (!red.empty()) memcpy(img.data() + o_red, red.data(), red.size() * sizeof(SlabRedSlot));
+  hipStream_t s = (hipStream_t)stream;
+  // upload only when the contents changed (workspace and parameter addresses are stable from step to step): the
+  // caller's host copy of what the device table holds says so. A changed table waits for its copy before the host
+  // copy may change again.
+  if (memcmp(table_host, img.data(), (size_t)bytes) != 0) {
+    memcpy(table_host, img.data(), (size_t)bytes);
+    if (hipMemcpyAsync(table, table_host, (size_t)bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+      memset(table_host, 0, sizeof(GroupHeader));
+      return SVAE_ELAUNCH;
+    }
+  }
+  const char* t = (const char*)table;
+  const GPSlot* tab = (const GPSlot*)(t + o_gp);
+  if (!map[0].empty()) {
+    hipLaunchKernelGGL((gemm256_group_kernel<SVAE_EPI_F32_ACC>), dim3((unsigned)map[0].size()), dim3(512), 0, s, tab,
+                       (const GMap*)(t + o_ma));
+    SVAE_LAUNCH_CHECK();
+  }
+  if (!map[1].empty()) {
+    hipLaunchKernelGGL((gemm256_group_kernel<G3_EPI_SLAB>), dim3((unsigned)map[1].size()), dim3(512), 0, s, tab,
+                       (const GMap*)(t + o_mb));
+    SVAE_LAUNCH_CHECK();
+    const long long rb = std::max(1LL, std::min(2048LL, (red_elems + 255) / 256));
+    hipLaunchKernelGGL(slab_reduce_list_kernel, dim3((unsigned)rb), dim3(256), 0, s, (const SlabRedSlot*)(t + o_red),
+                       (int)red.size());
+    SVAE_LAUNCH_CHECK();
+  }
   return SVAE_OK;
 }
 

@@ -67,6 +67,7 @@ class AttnDesc(ctypes.Structure):
     ]
 
 
+GROUP_MAX = 256         # SVAE_GROUP_MAX
 COLSUM_MAX = 8
 LN_MULTI_MAX = 4        # SVAE_LN_MULTI_MAX
 
@@ -92,6 +93,8 @@ class ColsumSeg(ctypes.Structure):
 _SIGS = {
     'svae_gemm': [ctypes.POINTER(GemmDesc), c_void_p],
     'svae_gemm_pair': [ctypes.POINTER(GemmDesc), ctypes.POINTER(GemmDesc), c_void_p],
+    'svae_gemm_group_table_bytes': [c_int32],
+    'svae_gemm_group': [ctypes.POINTER(GemmDesc), c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p],
     'svae_resid_ln_fwd': [c_void_p, c_void_p, c_int32, c_int64, c_float, c_uint64, c_void_p, c_int32, c_void_p,
                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p],
     'svae_layernorm_fwd': [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
@@ -195,7 +198,8 @@ def _load():
         fn.argtypes = argtypes
         fn.restype = {'svae_version': ctypes.c_char_p, 'svae_attn_dq_part_elems': c_int64,
                       'svae_attn_dq_part_elems_w': c_int64, 'svae_attn_fwd_ws_elems': c_int64,
-                      'svae_latent_topk_ws_bytes': c_int64}.get(name, ctypes.c_int)
+                      'svae_latent_topk_ws_bytes': c_int64,
+                      'svae_gemm_group_table_bytes': c_int64}.get(name, ctypes.c_int)
     return lib
 
 

@@ -20,7 +20,7 @@ from collections import OrderedDict
 import torch
 
 from . import kernels as K
-from ._native import COLSUM_MAX, LN_MULTI_MAX, ZPROJ_MAX
+from ._native import COLSUM_MAX, GROUP_MAX, LN_MULTI_MAX, ZPROJ_MAX
 from ._native import EPI_BF16, EPI_F32, EPI_F32_ACC, EPI_GELU, EPI_GELU_BWD, EPI_DROPOUT_RESID, \
     EPI_ROTARY_BF16, EPI_CE_STATS, EPI_F32_ATOMIC, EPI_CE_PROB, EPI_ROWSCALE_GATHER
 
@@ -262,6 +262,15 @@ class VAEEngine:
         # the two dW GEMMs of the FFN, and the attention output projection's with the Q/K/V projection's, run as one
         # paired launch each (kernels.linear_dw_pair); SVAE_DW_PAIR=0 launches them one by one (A/B runs)
         self.dw_pair = os.environ.get('SVAE_DW_PAIR', '1') != '0'
+        # every layer's weight-gradient GEMMs deferred to one grouped pass at the end of the backward
+        # (kernels.linear_dw_group: the chip filled across layers instead of across K; the layers' dY buffers are then
+        # per-layer workspace). Not with data-parallel hooks (the bucketed all-reduce needs the gradients in ready
+        # order) or the side stream; SVAE_DW_GROUP=0 restores the per-layer launches (A/B runs)
+        self.dw_group = os.environ.get('SVAE_DW_GROUP', '1') != '0'
+        self._dw_jobs = []          # the deferred jobs of this backward
+        self._dwq = None            # = _dw_jobs while a layer_bwd records into it (else None: _dw launches in place)
+        self._dw_names = False      # this backward keeps the layers' dY operands in per-layer buffers
+        self._dwg_states, self._dwg_sched = [], {}
         # decoder residual adds in a separate fused residual + dropout + LayerNorm pass (layer_fwd's fuse, SVAE_FUSE_LN=1)
         # instead of the projections' f32 residual epilogues + LayerNorm passes. Off by default: measured at C2 it moves
         # 36 B per element and layer against 28 (the projection output makes an f32 round trip), +0.125 ms of kernel
@@ -371,6 +380,9 @@ class VAEEngine:
             off = self.P.offsets[bias][0]
             bg = self.P.grad[off:off + n_out]
         side = self.side if on_side else None
+        if self._dwq is not None and on_side and rows >= K.GROUP_MIN_ROWS:
+            self._dwq.append((dY, X, self.P.g(wname), rows, n_out, n_in, ldy, ldx, bg))
+            return
         if side is None:
             K.linear_dw(dY, X, self.P.g(wname), rows, n_out, n_in, ldy, ldx, bgrad=bg)
             return
@@ -396,7 +408,7 @@ class VAEEngine:
     def _dw_pair(self, j0, j1):
         """Two _dw's ((dY, X, wname, rows, n_out, n_in[, ldy, ldx, bias])) in one paired launch (svae_gemm_pair):
         half the split-K slab traffic of two separate launches. SVAE_DW_PAIR=0 (or the side stream) runs them apart."""
-        if self.side is not None or not self.dw_pair:
+        if self._dwq is not None or self.side is not None or not self.dw_pair:
             for j in (j0, j1):
                 self._dw(*j[:6], *(tuple(j[6:]) + (None,) * (9 - len(j))))
             return
@@ -410,6 +422,26 @@ class VAEEngine:
                 bg = self.P.grad[off:off + n_out]
             args.append((dY, X, self.P.g(wname), rows, n_out, n_in, ldy, ldx, bg))
         K.linear_dw_pair(*args)
+
+    def _bname(self, name, st):
+        """Workspace name of a layer_bwd buffer a weight-gradient GEMM reads: per layer while those GEMMs are deferred
+        (the buffer has to outlive its layer), else shared by all layers."""
+        return f'{name}.{st["tag"]}' if self._dw_names else name
+
+    def flush_dw(self):
+        """The deferred weight-gradient GEMMs, all in one grouped pass (kernels.group_schedule's fixed schedule)."""
+        q, self._dw_jobs = self._dw_jobs, []
+        k = 0   # each call of the schedule keeps its own parameter table (unchanged from step to step)
+        for c in range(0, len(q), GROUP_MAX):
+            jobs = q[c:c + GROUP_MAX]
+            key = tuple((j[4], j[5], j[3]) for j in jobs)
+            if key not in self._dwg_sched:
+                self._dwg_sched[key] = K.group_schedule(key, self.ncu)
+            for idx, splits, slab in self._dwg_sched[key]:
+                if len(self._dwg_states) <= k:
+                    self._dwg_states.append(K.DwGroupState(self.P.device))
+                K.linear_dw_group([jobs[i] for i in idx], splits, self._dwg_states[k], slab=slab)
+                k += 1
 
     def join_side(self):
         """The caller's stream waits for every weight-gradient GEMM issued so far."""
@@ -563,12 +595,13 @@ class VAEEngine:
         return t if t is not None and t.numel() >= n else self.ws.get('b.dqpart', (n,), f32)
 
     def layer_bwd(self, st, dout, dx_out, *, dx_accumulate=False, dctx=None, g2_ready=False, next_drop=None,
-                  zsplice=None):
+                  zsplice=None, next_st=None):
         """Backward of layer_fwd. dout f32 [B*Lq, d] (consumed as scratch). Writes d x into dx_out
         (accumulating into it when dx_accumulate and the layer has no residual); cross-attention context
         gradients accumulate into dctx. g2_ready: the dropout-masked bf16 dout is already in the 'b.g2' buffer
         (written by the previous layer_bwd's last LayerNorm backward); next_drop = (p, seed, zero_mod): this
-        layer's last LayerNorm backward writes that buffer for the next layer_bwd (residual layers only).
+        layer's last LayerNorm backward writes that buffer for the next layer_bwd (residual layers only), the layer
+        with the saved state next_st (the buffer is per layer while the weight-gradient GEMMs are deferred, _bname).
         zsplice = (L, zrow, zrow_bf): that LayerNorm backward also moves rows r % L == 0 of dx_out into zrow / zrow_bf
         and zeroes them (the z splice's gradient, extract_rows + cast_bf16)."""
         d, ws, P = self.d, self.ws, self.P
@@ -578,10 +611,12 @@ class VAEEngine:
         rot = self.rot(max(Sx, L), st['window'])
         a = pre + 'attention.'
         # ---- FFN (transformer_layer.py:56-61)
-        g2 = ws.get('b.g2', (rows_q, d))
+        bn = lambda name: self._bname(name, st)   # noqa: E731
+        self._dwq = self._dw_jobs if self._dw_names else None
+        g2 = ws.get(bn('b.g2'), (rows_q, d))
         if not g2_ready:
             K.dropout_bwd_cast(dout, g2, st['drop_p'], st['seed'], rows_q, d)
-        dpre = ws.get('b.dpre', (rows_q, 4 * d))
+        dpre = ws.get(bn('b.dpre'), (rows_q, 4 * d))
         K.gemm(g2, P.wT(pre + 'ffn.2.weight', d, 4 * d), dpre, rows_q, 4 * d, d, epi=EPI_GELU_BWD, aux=st['gprime'],
                ldaux=4 * d)
         # (g2 stays intact until the next layer's backward)
@@ -590,7 +625,7 @@ class VAEEngine:
         dh2 = ws.get('b.dh2', (rows_q, d))
         K.gemm(dpre, P.wT(pre + 'ffn.0.weight', 4 * d, d), dh2, rows_q, d, 4 * d, epi=EPI_BF16)
         dxc = ws.get('b.dxc', (rows_q, d), f32)
-        gxc = ws.get('b.gxc', (rows_q, d))
+        gxc = ws.get(bn('b.gxc'), (rows_q, d))
         self._ln_bwd(pre + 'ffn_layer_norm', dh2, st['ln_f'], rows_q, dout, dxc, gxc)
         dx1, gx1 = dxc, gxc
         if st['cross']:
@@ -601,8 +636,8 @@ class VAEEngine:
             # the dO GEMM also writes delta = rowsum(dO . O) per head (its epilogue holds dO; no separate pass)
             K.gemm(gxc, P.wT(c + 'output_linear.weight', d, d), dOc, rows_q, d, d, epi=EPI_BF16, delta=delta if self.delta_fused else None,
                    delta_o32=st['Ocx'].get('o32'), ld_o32=d, delta_hd=hd, delta_seq=Lq)
-            dqc = ws.get('b.dqc', (rows_q, d))
-            dkvc = ws.get('b.dkvc', (rows_c, 2 * d))
+            dqc = ws.get(bn('b.dqc'), (rows_q, d))
+            dkvc = ws.get(bn('b.dkvc'), (rows_c, 2 * d))
             K.attention(st['qc'], st['kvc'], st['kvc'][:, d:], st['Oc'], st['lsec'], B=B, H=heads, Lq=Lq, Lk=L,
                         hd=hd, sq=d, bq=Lq * d, sk=2 * d, sv=2 * d, bk=L * 2 * d, bv=L * 2 * d, so=d, bo=Lq * d,
                         key_pad=st['pad_ctx'], causal=False, backward=True, delta_ready=self.delta_fused,
@@ -619,7 +654,7 @@ class VAEEngine:
             dcx = ws.get('b.dcx.' + st['tag'] if st.get('ctx_deferred') else 'b.dcx', (rows_c, d))
             K.gemm(dkvc, P.wT(c + 'k_linear.weight', 2 * d, d), dcx, rows_c, d, 2 * d, epi=EPI_BF16)
             dx1 = ws.get('b.dx1', (rows_q, d), f32)
-            gx1 = ws.get('b.gx1', (rows_q, d))
+            gx1 = ws.get(bn('b.gx1'), (rows_q, d))
             self._ln_bwd(pre + 'cross_attn_layer_norm', dhq, st['ln_cross'], rows_q, dxc, dx1, gx1)
             if st.get('ctx_deferred'):
                 st['dcx'] = dcx
@@ -634,7 +669,7 @@ class VAEEngine:
         if st['learned']:
             kv = st['kv']
             dq32 = ws.get('b.dq32', (B * Lq, d), f32)
-            dkv = ws.get('b.dkv', (rows_x, 2 * d))
+            dkv = ws.get(bn('b.dkv'), (rows_x, 2 * d))
             K.attention(P.w(a + 'learned_queries').view(Lq, d), kv, kv[:, d:], st['O'], st['lse'], B=B, H=heads,
                         Lq=Lq, Lk=Sx, hd=hd, sq=d, bq=0, sk=2 * d, sv=2 * d, bk=Sx * 2 * d, bv=Sx * 2 * d, so=d,
                         bo=Lq * d, key_pad=st['pad_k'], causal=False, backward=True, dout=dO, sdo=d, bdo=Lq * d,
@@ -648,7 +683,7 @@ class VAEEngine:
             K.gemm(dkv, P.wT(a + 'k_linear.weight', 2 * d, d), dh, rows_x, d, 2 * d, epi=EPI_BF16)
         else:
             qkv = st['qkv']
-            dqkv = ws.get('b.dqkv', (rows_x, 3 * d))
+            dqkv = ws.get(bn('b.dqkv'), (rows_x, 3 * d))
             K.attention(qkv, qkv[:, d:], qkv[:, 2 * d:], st['O'], st['lse'], B=B, H=heads, Lq=Lq, Lk=Sx, hd=hd,
                         sq=3 * d, bq=Sx * 3 * d, sk=3 * d, sv=3 * d, bk=Sx * 3 * d, bv=Sx * 3 * d, so=d, bo=Lq * d,
                         key_pad=st['pad_k'], causal=st['causal'], window=st['window'], backward=True, dout=dO,
@@ -663,12 +698,14 @@ class VAEEngine:
         if st['resid']:
             # the next layer's dropout-masked bf16 dout and the z splice's rows ride along (no separate passes)
             self._ln_bwd(pre + 'attn_layer_norm', dh, st['ln_a'], rows_x, dx1, dx_out,
-                         dx_bf=ws.get('b.g2', (rows_x, d)) if next_drop is not None else None, bf_drop=next_drop,
+                         dx_bf=(ws.get(self._bname('b.g2', next_st or st), (rows_x, d)) if next_drop is not None
+                                else None), bf_drop=next_drop,
                          zsplice=zsplice)
             if dx_accumulate:
                 raise NotImplementedError('residual + accumulate is handled by the caller')
         else:
             self._ln_bwd(pre + 'attn_layer_norm', dh, st['ln_a'], rows_x, dx_out if dx_accumulate else None, dx_out)
+        self._dwq = None
 
     # ------------------------------------------------------------------ full step
     def forward(self, ids, ntok, *, pad=True, eps=None, seed=0, kl_weight=1.0, dropout=0.1, need_logits=False):
@@ -1082,6 +1119,9 @@ class VAEEngine:
                 user_ready(end)
         if sv is None:
             raise RuntimeError('backward() without a saved forward')
+        # the layers' weight-gradient GEMMs: recorded by layer_bwd, launched as one group after the encoder (flush_dw)
+        self._dwq, self._dw_jobs = None, []
+        self._dw_names = self.dw_group and user_ready is None and self.side is None
         B, L = sv['B'], sv['L']
         T, V, Z, N = B * L, hp.vocab_size, hp.latent_depth, hp.num_latents
         gs = ws.get('gscale', (2,), f32)
@@ -1139,7 +1179,7 @@ class VAEEngine:
         top = sv['dec_layers'][-1]
         g2_pre = self.head_g2 and top['rows_q'] == T
         K.gemm(dpre0, P.wT('output_layer.0.weight', d, d), dx, T, d, d, epi=EPI_F32,
-               aux=ws.get('b.g2', (T, d)) if g2_pre else None, ldaux=d if g2_pre else 0,
+               aux=ws.get(self._bname('b.g2', top), (T, d)) if g2_pre else None, ldaux=d if g2_pre else 0,
                drop_p=top['drop_p'] if g2_pre else 0.0, seed=top['seed'] if g2_pre else 0)
         ready(P.end('output_layer.3.bias'))
 
@@ -1161,7 +1201,8 @@ class VAEEngine:
             # the layer's last LayerNorm backward when it is a residual layer)
             dzh_i = ws.get('b.dzh_all', (hp.num_layers, B, d), f32)[i] if self.zp_batch else dzh
             zs = (L, dzh_i, None) if st['resid'] and st['rows_q'] == T else None
-            self.layer_bwd(st, dx, dx_prev, g2_ready=g2_ready, next_drop=nd, zsplice=zs)
+            self.layer_bwd(st, dx, dx_prev, g2_ready=g2_ready, next_drop=nd, zsplice=zs,
+                           next_st=sv['dec_layers'][i - 1] if nd is not None else None)
             g2_ready = nd is not None
             wz, bz = f'z_projections.{i}.weight', f'z_projections.{i}.bias'
             if zs is not None and self.zp_batch:
@@ -1213,10 +1254,12 @@ class VAEEngine:
         if st0['resid']:   # L == num_latents: the first layer keeps its residual (transformer_layer.py:49)
             tmp = ws.get('b.dfirst', (T, d), f32)
             self.layer_bwd(st0, dcur, tmp)
+            self.flush_dw()
             self.join_side()        # the tied weight's head gradient (side stream) before the scatter-add
             K.embedding_bwd(sv['ids32'], tmp, P.g('input_layer.0.weight'), T, d)   # (the head's part: below)
         else:
             self.layer_bwd(st0, dcur, dx_emb, dx_accumulate=True)
+            self.flush_dw()     # every layer's weight gradients, before the scatter-add and anything that reads them
 
         ready(P.end('encoder.first_layer.ffn_layer_norm.bias'))
         # ---- embedding (tied with the head weight)

@@ -169,6 +169,103 @@ def linear_dw_pair(j0, j1):
     gemm_pair(*gs)
 
 
+GROUP_SLICE_MAX = 16384   # rows of a grouped K slice at most: above it the split GEMMs run several rounds of these
+GROUP_MIN_ROWS = 128      # a dW over fewer rows is not worth deferring (the engine launches it in place)
+
+
+def group_schedule(shapes, ncu=256):
+    """The fixed schedule of the grouped weight-gradient pass over GEMMs ((n_out, n_in, rows) each, in launch order):
+    a list of linear_dw_group calls, each (indices, splits, slab) over the GEMMs it takes.
+
+    Rounds of whole-K 256 x 256 tiles first, one call each: the GEMMs over the most rows, whole GEMMs in order while
+    their tiles fit one per compute unit, a round kept only if it fills at least 3/4 of the chip (C2: one round, 5 1/3
+    decoder layers, 256 tiles; C4 / C5, 12 layers of 108 tiles: five rounds of 252). A call never holds more whole-K
+    tiles than compute units (a whole-K tile is the longest unit there is, so a partly filled second round inside a
+    launch would cost a full tile time: asserted here, refused by svae_gemm_group). What no full round takes is cut
+    into K slices of one common length, the work divided by the compute units, so that they fill the chip in one
+    round as well (slices >= 512 rows, <= GROUP_SLICE_MAX), in the last call. The sliced GEMMs store slabs (also a
+    GEMM that ends up with a single slice: slab = True)."""
+    n = len(shapes)
+    tiles = [-(-m // 256) * -(-k // 256) for m, k, _ in shapes]
+    rows = [r for _, _, r in shapes]
+    splits, slab = [0] * n, [True] * n
+    rmax, calls = max(rows), []
+    while True:
+        used, rnd = 0, []
+        for i in range(n):
+            if splits[i] == 0 and rows[i] == rmax and used + tiles[i] <= ncu:
+                rnd.append(i)
+                used += tiles[i]
+        if 4 * used < 3 * ncu:
+            break
+        for i in rnd:
+            splits[i], slab[i] = 1, False
+        calls.append(rnd)
+    rest = [i for i in range(n) if splits[i] == 0]
+    if rest:
+        units = lambda sl: sum(tiles[i] * -(-rows[i] // sl) for i in rest)   # noqa: E731
+        work = sum(tiles[i] * rows[i] for i in rest)
+        sl = min(GROUP_SLICE_MAX, max(512, -(-work // (ncu * 64)) * 64))
+        while sl < GROUP_SLICE_MAX and units(sl) > ncu:
+            sl += 64
+        for i in rest:
+            s = -(-rows[i] // sl)
+            kchunk = -(-(-(-rows[i] // s)) // 64) * 64   # the kernel's slice: a multiple of 64 rows
+            splits[i] = -(-rows[i] // kchunk)            # (only the non-empty slices)
+        if calls:
+            calls[-1] = calls[-1] + rest
+        else:
+            calls.append(rest)
+    for c in calls:
+        assert sum(tiles[i] for i in c if not slab[i]) <= ncu, 'a second round of whole-K tiles in one launch'
+    return [(c, [splits[i] for i in c], [slab[i] for i in c]) for c in calls]
+
+
+class DwGroupState:
+    """What svae_gemm_group keeps between calls, owned by the caller: the descriptor array, the device parameter
+    table and the host copy of it (the table is uploaded only when its contents change)."""
+
+    def __init__(self, device):
+        self.device, self.n = device, 0
+
+    def ensure(self, n):
+        if n > self.n:
+            self.n = max(n, 2 * self.n)
+            self.bytes = lib.svae_gemm_group_table_bytes(min(self.n, N.GROUP_MAX))
+            self.descs = (N.GemmDesc * self.n)()
+            self.table = torch.empty(self.bytes, dtype=torch.uint8, device=self.device)
+            self.host = ctypes.create_string_buffer(self.bytes)   # (zeroed)
+
+
+def linear_dw_group(jobs, splits, state, slab=None, max_blocks=0):
+    """linear_dw for every job ((dY, X, Wgrad, rows, n_out, n_in, ldy, ldx, bgrad) each) in one grouped pass
+    (svae_gemm_group): the jobs with slab[i] false (default: splits[i] == 1) accumulate whole-K tiles straight into
+    Wgrad in one launch; the others store splits[i] K slices into slabs in a second launch, added into Wgrad in slice
+    order by one reduction launch. max_blocks > 0 caps the blocks per launch (they then walk several tiles each)."""
+    n = len(jobs)
+    if n == 0:
+        return
+    if n > N.GROUP_MAX:
+        raise RuntimeError(f'linear_dw_group: {n} GEMMs (at most {N.GROUP_MAX})')
+    slab = [s > 1 for s in splits] if slab is None else slab
+    need = sum(s * j[4] * j[5] for j, s, sb in zip(jobs, splits, slab) if sb)
+    ws = _slab_workspace(need, jobs[0][0].device) if need else None
+    state.ensure(n)
+    off = 0
+    for i, (j, s, sb) in enumerate(zip(jobs, splits, slab)):
+        dY, X, Wg, rows, n_out, n_in, ldy, ldx, bg = j
+        aux = None
+        if sb:
+            aux = ws[off:off + s * n_out * n_in]
+            off += s * n_out * n_in
+        elif s != 1:
+            raise RuntimeError('linear_dw_group: a GEMM without a slab has one split')
+        _fill_desc(state.descs[i], dY, X, Wg, n_out, n_in, rows, a_t=True, b_t=True, lda=ldy or n_out, ldb=ldx or n_in,
+                   ldc=n_in, epi=N.EPI_F32_ATOMIC if sb else N.EPI_F32_ACC, splits=s, a_rowsum=bg, aux=aux)
+    check(lib.svae_gemm_group(state.descs, n, max_blocks, state.table.data_ptr(), state.host, state.bytes, stream()),
+          'svae_gemm_group')
+
+
 _slabs = {}
 
 
