@@ -477,6 +477,48 @@ int svae_dec_sample(const float* logits, int64_t ldl, int32_t V, int32_t rows, c
                     svae_stream_t stream);
 int svae_dec_advance(int32_t* cur, svae_stream_t stream);
 
+/* ---- streaming bulk sampling: the decode kernels with one position per row ("slot"), StreamDecoder's step.
+ * Same kernel bodies and arithmetic as the dec_* forms: with every pos[s] = c and key[s] = s the results equal
+ * the dec_* forms' at cur = c bit for bit. pos: device int32 [S], the slot's current_index (>= 1); 0 = idle slot,
+ * which every kernel skips without touching the slot's outputs; < 0 = finished, waiting for slot_refill. ids:
+ * int64 [S][T], a slot's own output_ids row. T <= 32768.
+ * slot_linear: dec_linear with the rotary epilogue at position pos[m]-1 of each row (same K-slicing, split rule,
+ *   reduction order and finalize; the other epilogues take no position: use svae_dec_linear).
+ * slot_attn: dec_attn with p = pos[s]-1 per slot: appends k, v at p, attends over the keys visible from p.
+ * slot_embed: x[s] = table[ids[s][pos[s]-1]].
+ * slot_splice: x[s] = zp[s] for the slots with pos[s] == 1 (the layer input of a sample's first step is
+ *   z_projections[layer](z), transformer_vae.py:117-121); x f32 [S][D], zp f32 [S][ldz] (ldz >= D: one layer's
+ *   columns of all layers' projections side by side), D % 4 == 0, ldz % 4 == 0, 16-byte aligned.
+ * slot_penalty: dec_penalty over the slot's own ids[s][max(pos-512,0) .. pos-1].
+ * slot_sample: dec_sample per slot; the multinomial draw is keyed by (seed, pos[s], key[s]) where key[s] is the
+ *   number of the sample in the slot, so a sample's draws do not depend on the slot it ran in. Writes the token to
+ *   ids[s][pos[s]] and as int16 to out[key[s]][pos[s]-1] (out: int16 [num_samples][T-1], zeroed by the caller),
+ *   then pos[s] += 1, or pos[s] = -1 when the sample ended: the token is end_token, or position T-2 was written
+ *   (KVDecoder.run's bound: the last column of a full-length row stays 0). V <= 32768.
+ * slot_refill: one workgroup, no atomics. Every finished slot (pos < 0), in slot order, counts into *completed if
+ *   it held a sample (key >= 0) and takes the next sample number j = (*next)++: if j < num_samples then key[s] = j,
+ *   pos[s] = 1, ids[s][0] = start_token, z_slot[s] = z_all[j] (f32 rows of Z); else pos[s] = 0. *next never passes
+ *   num_samples. The initial fill is this call on pos = -1, key = -1, *next = 0. */
+int svae_slot_linear(const float* X, int64_t ldx, const float* W, int64_t ldw, const float* bias, float* Y, int64_t ldy,
+                     const float* resid, int64_t ldr, int32_t S, int32_t N, int32_t K, const float* rot_tab,
+                     int32_t rot_cols, int32_t rot_d, const int32_t* pos, float* part_ws, int64_t part_elems,
+                     svae_stream_t stream);
+int svae_slot_attn(const float* qkv, int64_t ldq, float* kcache, float* vcache, int32_t S, int32_t H, int32_t hd,
+                   int32_t T, const int32_t* pos, int32_t window, float scale, float* O, int64_t ldo,
+                   svae_stream_t stream);
+int svae_slot_embed(const int64_t* ids, int32_t T, const int32_t* pos, const float* table, float* x, int32_t S,
+                    int32_t D, svae_stream_t stream);
+int svae_slot_splice(float* x, const float* zp, int64_t ldz, const int32_t* pos, int32_t S, int32_t D,
+                     svae_stream_t stream);
+int svae_slot_penalty(float* logits, int64_t ldl, int32_t S, const int64_t* ids, int32_t T, const int32_t* pos,
+                      float penalty, svae_stream_t stream);
+int svae_slot_sample(const float* logits, int64_t ldl, int32_t V, int32_t S, int64_t* ids, int32_t T, int32_t* pos,
+                     const int32_t* key, int16_t* out, int32_t num_samples, int32_t end_token, float temperature,
+                     int32_t top_k, float top_p, uint64_t seed, svae_stream_t stream);
+int svae_slot_refill(int32_t* pos, int32_t* key, int64_t* ids, int32_t T, int32_t S, int32_t start_token,
+                     const float* z_all, float* z_slot, int32_t Z, int32_t num_samples, int32_t* next,
+                     int32_t* completed, svae_stream_t stream);
+
 /* ---- latent index: posterior gathering and k-NN search (gather_latents.py:26-31, knn.py:28-50,
  * math_utils.py:90-101) -------------------------------------------------------------------------------
  * A corpus is N posteriors q(z|x) = N(mu, scale^2), f32 [N][Z]; Z % 4 == 0, 4 <= Z <= 256, N >= 1 (int32); mu,

@@ -17,12 +17,25 @@
 //   svae_dec_sample:  greedy / temperature / top-k / top-p (nucleus) + multinomial with a counter-based RNG,
 //                     writes out_ids[b][cur], updates the live mask (generation.py:43-77).
 //   svae_dec_advance: cur += 1.
+//
+// Streaming bulk sampling (StreamDecoder) runs the same kernel bodies with one position per row ("slot"): the
+// svae_slot_* forms read pos[row] where the svae_dec_* forms read *cur (template parameter SLOT), skip idle slots
+// (pos == 0) and key the multinomial draw by the sample number the slot holds instead of by the row.
+//   svae_slot_splice: rows at position 1 take the layer input from z_projections[layer](z) (transformer_vae.py:119-121).
+//   svae_slot_refill: one workgroup hands the finished slots, in slot order, the next sample numbers.
 #include "common.h"
 #include "../../include/svae.h"
 
 using namespace svae;
 
 namespace {
+
+// Where a row's position (GenerationState.current_index) comes from: the scalar the whole batch shares, or the
+// row's own entry of a per-slot array (0 = idle slot, < 0 = finished and waiting for svae_slot_refill).
+template <bool SLOT>
+__device__ __forceinline__ int row_pos(const int* cur, int row) {
+  return SLOT ? cur[row] : *cur;
+}
 
 // ------------------------------------------------------------------ skinny f32 linear
 // 16 output columns x up to 64 rows per workgroup of 16 waves; the waves split the workgroup's K range and meet in
@@ -40,7 +53,7 @@ struct DL {
   const float* resid; long long ldr;
   int M, N, K, kslice;
   const float* rot; int rot_cols, rot_d;
-  const int* cur;
+  const int* cur;     // the shared position, or with SLOT one position per row
   float* part;        // [splits][M][N] partial sums (split-K), or nullptr
 };
 
@@ -69,7 +82,7 @@ __device__ __forceinline__ void dl_epilogue(const DL& p, int m, int nn, float x0
   if (nn + 1 < p.N) p.Y[(long long)m * p.ldy + nn + 1] = x1;
 }
 
-template <int EPI>
+template <int EPI, bool SLOT>
 __global__ __launch_bounds__(1024) void dec_linear_kernel(DL p) {
   __shared__ float red[DL_WAVES][DL_MROWS][17];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -136,11 +149,13 @@ __global__ __launch_bounds__(1024) void dec_linear_kernel(DL p) {
     if (nn + 1 < p.N) pp[1] = x1;
     return;
   }
-  dl_epilogue<EPI>(p, m, nn, x0, x1, p.cur ? *p.cur - 1 : 0);
+  const int pos = p.cur ? row_pos<SLOT>(p.cur, m) - 1 : 0;
+  if (SLOT && pos < 0) return;                 // idle slot: its output row stays as it is
+  dl_epilogue<EPI>(p, m, nn, x0, x1, pos);
 }
 
 // split-K finalize: thread = (row, column pair), the splits added in order, then the epilogue
-template <int EPI>
+template <int EPI, bool SLOT>
 __global__ __launch_bounds__(256) void dec_linear_finalize_kernel(DL p, int splits) {
   const int half = (p.N + 1) / 2;
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -152,7 +167,9 @@ __global__ __launch_bounds__(256) void dec_linear_finalize_kernel(DL p, int spli
     x0 += pp[0];
     if (nn + 1 < p.N) x1 += pp[1];
   }
-  dl_epilogue<EPI>(p, m, nn, x0, x1, p.cur ? *p.cur - 1 : 0);
+  const int pos = p.cur ? row_pos<SLOT>(p.cur, m) - 1 : 0;
+  if (SLOT && pos < 0) return;
+  dl_epilogue<EPI>(p, m, nn, x0, x1, pos);
 }
 
 // ------------------------------------------------------------------ block reductions (256 / 1024 threads)
@@ -188,6 +205,7 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {
 // more cache rows in flight than with 4 waves (the sweep is load-latency bound)
 constexpr int DA_THREADS = 1024, DA_WAVES = DA_THREADS / 64;
 
+template <bool SLOT>
 __global__ __launch_bounds__(DA_THREADS) void dec_attn_kernel(const float* __restrict__ qkv, long long ldq,
                                                        float* __restrict__ kc, float* __restrict__ vc, int H, int hd,
                                                        int T, const int* __restrict__ cur, int window, float scale,
@@ -196,7 +214,8 @@ __global__ __launch_bounds__(DA_THREADS) void dec_attn_kernel(const float* __res
   __shared__ float qs[128], ks[128], vs[128], red[2 * DA_WAVES], osum[DA_THREADS];
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int d = H * hd;
-  const int p = *cur - 1;
+  const int p = row_pos<SLOT>(cur, b) - 1;
+  if (SLOT && (p < 0 || p >= T)) return;       // idle slot (uniform over the workgroup, before any barrier)
   const float* qrow = qkv + (long long)b * ldq + h * hd;
   const long long cbase = ((long long)b * H + h) * T * hd;
   if (tid < hd) {
@@ -259,18 +278,22 @@ __global__ __launch_bounds__(DA_THREADS) void dec_attn_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------ embedding of the previous token
+template <bool SLOT>
 __global__ __launch_bounds__(256) void dec_embed_kernel(const long long* __restrict__ out_ids, int T,
                                                         const int* __restrict__ cur, const float* __restrict__ table,
                                                         float* __restrict__ x, int B, int D) {
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (b >= B) return;
-  const long long tok = out_ids[(long long)b * T + *cur - 1];
+  const int c0 = row_pos<SLOT>(cur, b);
+  if (SLOT && (c0 <= 0 || c0 > T)) return;
+  const long long tok = out_ids[(long long)b * T + c0 - 1];
   for (int c = lane * 4; c < D; c += 256) *(f32x4*)(x + (long long)b * D + c) = *(const f32x4*)(table + tok * D + c);
 }
 
 // ------------------------------------------------------------------ repetition penalty
 // One block per logits row; the gathers all happen before any write, so a token repeated in the window is
 // penalised once from its original value (torch gather then scatter_, generation.py:38-41).
+template <bool SLOT>
 __global__ __launch_bounds__(512) void dec_penalty_kernel(float* __restrict__ logits, long long ldl,
                                                           const int* __restrict__ row_map,
                                                           const long long* __restrict__ out_ids, int T,
@@ -278,7 +301,9 @@ __global__ __launch_bounds__(512) void dec_penalty_kernel(float* __restrict__ lo
                                                           const unsigned char* __restrict__ live, float penalty) {
   const int r = blockIdx.x, b = row_map ? row_map[r] : r;
   if (live && !live[b]) return;
-  const int c = *cur, left = max(c - 512, 0), nprev = c - left;
+  const int c = row_pos<SLOT>(cur, b);
+  if (SLOT && (c <= 0 || c > T)) return;
+  const int left = max(c - 512, 0), nprev = c - left;
   float* row = logits + (long long)r * ldl;
   const int i = threadIdx.x;
   long long tok = 0;
@@ -301,12 +326,18 @@ __device__ __forceinline__ unsigned fkey(float x) {     // order-preserving floa
 }
 
 // Thread t holds vocabulary entries t + 1024 e (e < 32): coalesced row loads, and index order = (e, t).
+// SLOT: row b is a slot at its own position pos[b] holding sample key[b]; the draw is keyed by (seed, pos, key), the
+// token also goes to out[key][pos - 1] (int16 [num_samples][T - 1]), and the slot's position advances or, when the
+// sample ends (end token, or position T - 2 written: the stopping rule of KVDecoder.run), becomes -1.
+template <bool SLOT>
 __global__ __launch_bounds__(1024) void dec_sample_kernel(const float* __restrict__ logits, long long ldl, int V,
                                                           const int* __restrict__ row_map, long long* __restrict__ out_ids,
                                                           int T, const int* __restrict__ cur,
                                                           unsigned char* __restrict__ live, int end_token,
                                                           float temperature, int top_k, float top_p, uint64_t seed,
-                                                          int* __restrict__ live_count) {
+                                                          int* __restrict__ live_count, int* __restrict__ pos_out,
+                                                          const int* __restrict__ key, short* __restrict__ out,
+                                                          int num_samples) {
   __shared__ float shf[32 * (DS_T / 64)];
   __shared__ int shi[DS_T / 64];
   __shared__ float colsum[DS_E];
@@ -315,7 +346,8 @@ __global__ __launch_bounds__(1024) void dec_sample_kernel(const float* __restric
   const int r = blockIdx.x, b = row_map ? row_map[r] : r;
   if (live && !live[b]) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int c = *cur;
+  const int c = row_pos<SLOT>(cur, b);
+  if (SLOT && (c <= 0 || c >= T)) return;
   const float* row = logits + (long long)r * ldl;
   float x[DS_E];
 #pragma unroll
@@ -414,7 +446,7 @@ __global__ __launch_bounds__(1024) void dec_sample_kernel(const float* __restric
     __syncthreads();
     float tot = 0.f;
     for (int e = 0; e < DS_E; ++e) tot += colsum[e];
-    const float u = rand_uniform(seed, (uint64_t)c * 0x100000000ull + (uint64_t)b) * tot;
+    const float u = rand_uniform(seed, (uint64_t)c * 0x100000000ull + (uint64_t)(SLOT ? key[b] : b)) * tot;
     int ec = DS_E - 1;
     float before = 0.f;
     for (int e = 0; e < DS_E; ++e) {
@@ -469,26 +501,99 @@ __global__ __launch_bounds__(1024) void dec_sample_kernel(const float* __restric
   }
   if (tid == 0) {
     out_ids[(long long)b * T + c] = token;           // :71
-    const bool cont = token != end_token && c + 1 < T;   // :73-74 (current_index incremented first)
-    if (live && !cont) {
-      live[b] = 0;
-      if (live_count) atomicSub(live_count, 1);
+    if constexpr (SLOT) {
+      const int j = key[b];
+      if (j >= 0 && j < num_samples) out[(long long)j * (T - 1) + c - 1] = (short)token;
+      pos_out[b] = (token == end_token || c >= T - 2) ? -1 : c + 1;
+    } else {
+      const bool cont = token != end_token && c + 1 < T;   // :73-74 (current_index incremented first)
+      if (live && !cont) {
+        live[b] = 0;
+        if (live_count) atomicSub(live_count, 1);
+      }
     }
   }
 }
 
 __global__ void dec_advance_kernel(int* cur) { *cur += 1; }
 
+// ------------------------------------------------------------------ per-slot state
+// x[s] = zp[s] for the slots at position 1: the layer input of a sample's first step is z_projections[layer](z).
+__global__ __launch_bounds__(256) void slot_splice_kernel(float* __restrict__ x, const float* __restrict__ zp,
+                                                          long long ldz, const int* __restrict__ pos, int S, int D) {
+  const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (s >= S || pos[s] != 1) return;
+  for (int c = lane * 4; c < D; c += 256) *(f32x4*)(x + (long long)s * D + c) = *(const f32x4*)(zp + (long long)s * ldz + c);
+}
+
+// One workgroup walks the slots in order, 256 at a time. A finished slot (pos < 0) that held a sample (key >= 0)
+// counts as completed; it then takes sample number *next + (finished slots before it) if that is < num_samples
+// (key, position 1, start token, its z row), else goes idle. No atomics: the order is the slot order.
+constexpr int SR_T = 256;
+__global__ __launch_bounds__(SR_T) void slot_refill_kernel(int* __restrict__ pos, int* __restrict__ key,
+                                                           long long* __restrict__ ids, int T, int S, int start_token,
+                                                           const float* __restrict__ z_all, float* __restrict__ z_slot,
+                                                           int Z, int num_samples, int* __restrict__ next,
+                                                           int* __restrict__ completed) {
+  __shared__ int wfin[SR_T / 64], whad[SR_T / 64], assign[SR_T];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int base = min(*next, num_samples), done = 0;      // read by every thread before the first barrier
+  for (int s0 = 0; s0 < S; s0 += SR_T) {
+    const int s = s0 + tid;
+    const bool fin = s < S && pos[s] < 0;
+    const bool had = fin && key[s] >= 0;
+    const unsigned long long mf = __ballot(fin), mh = __ballot(had);
+    __syncthreads();
+    if (lane == 0) { wfin[w] = __popcll(mf); whad[w] = __popcll(mh); }
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int k = 0; k < SR_T / 64; ++k) {
+      if (k < w) off += wfin[k];
+      tot += wfin[k];
+      done += whad[k];
+    }
+    int a = -1;
+    if (fin) {
+      const int rank = off + __popcll(mf & ((1ull << lane) - 1));
+      if (rank < num_samples - base) {
+        a = base + rank;
+        key[s] = a;
+        pos[s] = 1;
+        ids[(long long)s * T] = start_token;
+      } else {
+        pos[s] = 0;
+      }
+    }
+    assign[tid] = a;
+    __syncthreads();
+    if (tot > 0) {
+      const int n = min(SR_T, S - s0);
+      for (int i = tid; i < n * Z; i += SR_T) {
+        const int sl = i / Z, c = i - sl * Z, j = assign[sl];
+        if (j >= 0) z_slot[(long long)(s0 + sl) * Z + c] = z_all[(long long)j * Z + c];
+      }
+    }
+    base += min(tot, num_samples - base);
+  }
+  if (tid == 0) {
+    *next = base;
+    *completed += done;
+  }
+}
+
 }  // namespace
 
-SVAE_EXPORT int svae_dec_linear(const float* X, int64_t ldx, const float* W, int64_t ldw, const float* bias, float* Y,
-                                int64_t ldy, const float* resid, int64_t ldr, int32_t M, int32_t N, int32_t K,
-                                int32_t epi, const float* rot_tab, int32_t rot_cols, int32_t rot_d, const int32_t* cur,
-                                float* part_ws, int64_t part_elems, svae_stream_t stream) {
+// svae_dec_linear / svae_slot_linear: one validation, split rule and launch for both position sources
+template <bool SLOT>
+static int dl_launch(const float* X, int64_t ldx, const float* W, int64_t ldw, const float* bias, float* Y, int64_t ldy,
+                     const float* resid, int64_t ldr, int32_t M, int32_t N, int32_t K, int32_t epi, const float* rot_tab,
+                     int32_t rot_cols, int32_t rot_d, const int32_t* cur, float* part_ws, int64_t part_elems,
+                     svae_stream_t stream) {
   if (!X || !W || !Y || M <= 0 || N <= 0 || K <= 0 || K % 4 || ldx % 4 || ldw % 4) return SVAE_EINVAL;
   if (((uintptr_t)X | (uintptr_t)W) & 15) return SVAE_EINVAL;
   if (epi == SVAE_EPI_ROTARY_BF16 && (!rot_tab || !cur || rot_d <= 0 || rot_d % 2 || rot_cols % 2)) return SVAE_EINVAL;
   if (epi != SVAE_EPI_F32 && epi != SVAE_EPI_GELU && epi != SVAE_EPI_ROTARY_BF16) return SVAE_EINVAL;
+  if (SLOT && epi != SVAE_EPI_ROTARY_BF16) return SVAE_EINVAL;
   const int cols = (N + 15) / 16, mblk = (M + DL_MROWS - 1) / DL_MROWS;
   // split K over workgroups until ~512 workgroups are in flight (slices of >= 256 K-elements), if a workspace
   // of splits * M * N floats was given
@@ -506,17 +611,38 @@ SVAE_EXPORT int svae_dec_linear(const float* X, int64_t ldx, const float* W, int
   const int fin_blocks = (M * ((N + 1) / 2) + 255) / 256;
 #define SVAE_DL_CASE(E)                                                                               \
   case E:                                                                                             \
-    hipLaunchKernelGGL((dec_linear_kernel<E>), grid, dim3(1024), 0, s, p);                            \
-    if (splits > 1) hipLaunchKernelGGL((dec_linear_finalize_kernel<E>), dim3(fin_blocks), dim3(256), 0, s, p, splits); \
+    hipLaunchKernelGGL((dec_linear_kernel<E, SLOT>), grid, dim3(1024), 0, s, p);                      \
+    if (splits > 1)                                                                                   \
+      hipLaunchKernelGGL((dec_linear_finalize_kernel<E, SLOT>), dim3(fin_blocks), dim3(256), 0, s, p, splits); \
     break;
-  switch (epi) {
-    SVAE_DL_CASE(SVAE_EPI_F32)
-    SVAE_DL_CASE(SVAE_EPI_GELU)
-    SVAE_DL_CASE(SVAE_EPI_ROTARY_BF16)
+  if constexpr (SLOT) {
+    switch (epi) { SVAE_DL_CASE(SVAE_EPI_ROTARY_BF16) }
+  } else {
+    switch (epi) {
+      SVAE_DL_CASE(SVAE_EPI_F32)
+      SVAE_DL_CASE(SVAE_EPI_GELU)
+      SVAE_DL_CASE(SVAE_EPI_ROTARY_BF16)
+    }
   }
 #undef SVAE_DL_CASE
   SVAE_LAUNCH_CHECK();
   return SVAE_OK;
+}
+
+SVAE_EXPORT int svae_dec_linear(const float* X, int64_t ldx, const float* W, int64_t ldw, const float* bias, float* Y,
+                                int64_t ldy, const float* resid, int64_t ldr, int32_t M, int32_t N, int32_t K,
+                                int32_t epi, const float* rot_tab, int32_t rot_cols, int32_t rot_d, const int32_t* cur,
+                                float* part_ws, int64_t part_elems, svae_stream_t stream) {
+  return dl_launch<false>(X, ldx, W, ldw, bias, Y, ldy, resid, ldr, M, N, K, epi, rot_tab, rot_cols, rot_d, cur, part_ws,
+                          part_elems, stream);
+}
+
+SVAE_EXPORT int svae_slot_linear(const float* X, int64_t ldx, const float* W, int64_t ldw, const float* bias, float* Y,
+                                 int64_t ldy, const float* resid, int64_t ldr, int32_t S, int32_t N, int32_t K,
+                                 const float* rot_tab, int32_t rot_cols, int32_t rot_d, const int32_t* pos,
+                                 float* part_ws, int64_t part_elems, svae_stream_t stream) {
+  return dl_launch<true>(X, ldx, W, ldw, bias, Y, ldy, resid, ldr, S, N, K, SVAE_EPI_ROTARY_BF16, rot_tab, rot_cols,
+                         rot_d, pos, part_ws, part_elems, stream);
 }
 
 SVAE_EXPORT int svae_dec_attn(const float* qkv, int64_t ldq, float* kcache, float* vcache, int32_t B, int32_t H,
@@ -525,7 +651,7 @@ SVAE_EXPORT int svae_dec_attn(const float* qkv, int64_t ldq, float* kcache, floa
   if (!qkv || !kcache || !vcache || !cur || !O || B <= 0 || H <= 0 || T <= 0) return SVAE_EINVAL;
   if (hd <= 0 || hd > 128 || hd % 4 || window < 0 || T > 32768) return SVAE_EINVAL;
   if ((((uintptr_t)kcache | (uintptr_t)vcache) & 15) || ldq % 4) return SVAE_EINVAL;
-  hipLaunchKernelGGL(dec_attn_kernel, dim3(H, B), dim3(DA_THREADS), (size_t)T * sizeof(float), (hipStream_t)stream, qkv, ldq,
+  hipLaunchKernelGGL(dec_attn_kernel<false>, dim3(H, B), dim3(DA_THREADS), (size_t)T * sizeof(float), (hipStream_t)stream, qkv, ldq,
                      kcache, vcache, H, hd, T, cur, window, scale, O, ldo);
   SVAE_LAUNCH_CHECK();
   return SVAE_OK;
@@ -534,7 +660,7 @@ SVAE_EXPORT int svae_dec_attn(const float* qkv, int64_t ldq, float* kcache, floa
 SVAE_EXPORT int svae_dec_embed(const int64_t* out_ids, int32_t T, const int32_t* cur, const float* table, float* x,
                                int32_t B, int32_t D, svae_stream_t stream) {
   if (!out_ids || !cur || !table || !x || B <= 0 || D <= 0 || D % 4) return SVAE_EINVAL;
-  hipLaunchKernelGGL(dec_embed_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(dec_embed_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream,
                      (const long long*)out_ids, T, cur, table, x, B, D);
   SVAE_LAUNCH_CHECK();
   return SVAE_OK;
@@ -544,7 +670,7 @@ SVAE_EXPORT int svae_dec_penalty(float* logits, int64_t ldl, int32_t rows, const
                                  const int64_t* out_ids, int32_t T, const int32_t* cur, const uint8_t* live,
                                  float penalty, svae_stream_t stream) {
   if (!logits || !out_ids || !cur || rows <= 0 || T <= 0) return SVAE_EINVAL;
-  hipLaunchKernelGGL(dec_penalty_kernel, dim3(rows), dim3(512), 0, (hipStream_t)stream, logits, ldl, row_map,
+  hipLaunchKernelGGL(dec_penalty_kernel<false>, dim3(rows), dim3(512), 0, (hipStream_t)stream, logits, ldl, row_map,
                      (const long long*)out_ids, T, cur, live, penalty);
   SVAE_LAUNCH_CHECK();
   return SVAE_OK;
@@ -555,8 +681,9 @@ SVAE_EXPORT int svae_dec_sample(const float* logits, int64_t ldl, int32_t V, int
                                 float temperature, int32_t top_k, float top_p, uint64_t seed, int32_t* live_count,
                                 svae_stream_t stream) {
   if (!logits || !out_ids || !cur || rows <= 0 || V <= 0 || V > DS_T * DS_E || T <= 0) return SVAE_EINVAL;
-  hipLaunchKernelGGL(dec_sample_kernel, dim3(rows), dim3(DS_T), 0, (hipStream_t)stream, logits, ldl, V, row_map,
-                     (long long*)out_ids, T, cur, live, end_token, temperature, top_k, top_p, seed, live_count);
+  hipLaunchKernelGGL(dec_sample_kernel<false>, dim3(rows), dim3(DS_T), 0, (hipStream_t)stream, logits, ldl, V, row_map,
+                     (long long*)out_ids, T, cur, live, end_token, temperature, top_k, top_p, seed, live_count,
+                     (int*)nullptr, (const int*)nullptr, (short*)nullptr, 0);
   SVAE_LAUNCH_CHECK();
   return SVAE_OK;
 }
@@ -564,6 +691,70 @@ SVAE_EXPORT int svae_dec_sample(const float* logits, int64_t ldl, int32_t V, int
 SVAE_EXPORT int svae_dec_advance(int32_t* cur, svae_stream_t stream) {
   if (!cur) return SVAE_EINVAL;
   hipLaunchKernelGGL(dec_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, cur);
+  SVAE_LAUNCH_CHECK();
+  return SVAE_OK;
+}
+
+// ------------------------------------------------------------------ per-slot forms (streaming bulk sampling)
+SVAE_EXPORT int svae_slot_attn(const float* qkv, int64_t ldq, float* kcache, float* vcache, int32_t S, int32_t H,
+                               int32_t hd, int32_t T, const int32_t* pos, int32_t window, float scale, float* O,
+                               int64_t ldo, svae_stream_t stream) {
+  if (!qkv || !kcache || !vcache || !pos || !O || S <= 0 || H <= 0 || T <= 0) return SVAE_EINVAL;
+  if (hd <= 0 || hd > 128 || hd % 4 || window < 0 || T > 32768) return SVAE_EINVAL;
+  if ((((uintptr_t)kcache | (uintptr_t)vcache) & 15) || ldq % 4) return SVAE_EINVAL;
+  hipLaunchKernelGGL(dec_attn_kernel<true>, dim3(H, S), dim3(DA_THREADS), (size_t)T * sizeof(float), (hipStream_t)stream,
+                     qkv, ldq, kcache, vcache, H, hd, T, pos, window, scale, O, ldo);
+  SVAE_LAUNCH_CHECK();
+  return SVAE_OK;
+}
+
+SVAE_EXPORT int svae_slot_embed(const int64_t* ids, int32_t T, const int32_t* pos, const float* table, float* x,
+                                int32_t S, int32_t D, svae_stream_t stream) {
+  if (!ids || !pos || !table || !x || S <= 0 || D <= 0 || D % 4 || T <= 0 || T > 32768) return SVAE_EINVAL;
+  if (((uintptr_t)table | (uintptr_t)x) & 15) return SVAE_EINVAL;
+  hipLaunchKernelGGL(dec_embed_kernel<true>, dim3((S + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const long long*)ids,
+                     T, pos, table, x, S, D);
+  SVAE_LAUNCH_CHECK();
+  return SVAE_OK;
+}
+
+SVAE_EXPORT int svae_slot_splice(float* x, const float* zp, int64_t ldz, const int32_t* pos, int32_t S, int32_t D,
+                                 svae_stream_t stream) {
+  if (!x || !zp || !pos || S <= 0 || D <= 0 || D % 4 || ldz < D || ldz % 4) return SVAE_EINVAL;
+  if (((uintptr_t)x | (uintptr_t)zp) & 15) return SVAE_EINVAL;
+  hipLaunchKernelGGL(slot_splice_kernel, dim3((S + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, zp, ldz, pos, S, D);
+  SVAE_LAUNCH_CHECK();
+  return SVAE_OK;
+}
+
+SVAE_EXPORT int svae_slot_penalty(float* logits, int64_t ldl, int32_t S, const int64_t* ids, int32_t T,
+                                  const int32_t* pos, float penalty, svae_stream_t stream) {
+  if (!logits || !ids || !pos || S <= 0 || T <= 0 || T > 32768) return SVAE_EINVAL;
+  hipLaunchKernelGGL(dec_penalty_kernel<true>, dim3(S), dim3(512), 0, (hipStream_t)stream, logits, ldl,
+                     (const int*)nullptr, (const long long*)ids, T, pos, (const unsigned char*)nullptr, penalty);
+  SVAE_LAUNCH_CHECK();
+  return SVAE_OK;
+}
+
+SVAE_EXPORT int svae_slot_sample(const float* logits, int64_t ldl, int32_t V, int32_t S, int64_t* ids, int32_t T,
+                                 int32_t* pos, const int32_t* key, int16_t* out, int32_t num_samples, int32_t end_token,
+                                 float temperature, int32_t top_k, float top_p, uint64_t seed, svae_stream_t stream) {
+  if (!logits || !ids || !pos || !key || !out || S <= 0 || V <= 0 || V > DS_T * DS_E) return SVAE_EINVAL;
+  if (T < 2 || T > 32768 || num_samples < 0) return SVAE_EINVAL;
+  hipLaunchKernelGGL(dec_sample_kernel<true>, dim3(S), dim3(DS_T), 0, (hipStream_t)stream, logits, ldl, V,
+                     (const int*)nullptr, (long long*)ids, T, (const int*)pos, (unsigned char*)nullptr, end_token,
+                     temperature, top_k, top_p, seed, (int*)nullptr, pos, key, (short*)out, num_samples);
+  SVAE_LAUNCH_CHECK();
+  return SVAE_OK;
+}
+
+SVAE_EXPORT int svae_slot_refill(int32_t* pos, int32_t* key, int64_t* ids, int32_t T, int32_t S, int32_t start_token,
+                                 const float* z_all, float* z_slot, int32_t Z, int32_t num_samples, int32_t* next,
+                                 int32_t* completed, svae_stream_t stream) {
+  if (!pos || !key || !ids || !z_slot || !next || !completed || S <= 0 || Z <= 0) return SVAE_EINVAL;
+  if (T < 2 || T > 32768 || num_samples < 0 || (num_samples > 0 && !z_all)) return SVAE_EINVAL;
+  hipLaunchKernelGGL(slot_refill_kernel, dim3(1), dim3(SR_T), 0, (hipStream_t)stream, pos, key, (long long*)ids, T, S,
+                     start_token, z_all, z_slot, Z, num_samples, next, completed);
   SVAE_LAUNCH_CHECK();
   return SVAE_OK;
 }

@@ -176,6 +176,17 @@ _SIGS = {
     'svae_dec_sample': [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
                         c_float, c_int32, c_float, c_uint64, c_void_p, c_void_p],
     'svae_dec_advance': [c_void_p, c_void_p],
+    'svae_slot_linear': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32,
+                         c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p],
+    'svae_slot_attn': [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32,
+                       c_float, c_void_p, c_int64, c_void_p],
+    'svae_slot_embed': [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p],
+    'svae_slot_splice': [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p],
+    'svae_slot_penalty': [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_float, c_void_p],
+    'svae_slot_sample': [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                         c_int32, c_float, c_int32, c_float, c_uint64, c_void_p],
+    'svae_slot_refill': [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32,
+                         c_void_p, c_void_p, c_void_p],
     'svae_mutual_info': [c_void_p, c_void_p, c_uint64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                          c_void_p],
     'svae_latent_prepare': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p],

@@ -14,6 +14,9 @@ the graph. Rows are independent, so the surviving rows' outputs are the same.
 
 The KV cache holds every position ([layers][B][H][T][hd] f32); with sparse_self_attention the attention kernel
 reads exactly the keys the reference's sliding-window cache keeps (attention.py:115-140).
+
+StreamDecoder (below) is the bulk generator: the same step with one position per row, finished rows refilled on
+the device with the next sample, for `TransformerVAE.sample_stream`.
 """
 import torch
 
@@ -128,4 +131,149 @@ class KVDecoder:
         st.live_count.copy_(saved[3])
         self.kc.copy_(saved[4])
         self.vc.copy_(saved[5])
+        self.graph = g
+
+
+class StreamDecoder:
+    """Bulk unconditional sampling (the reference's sample.py + batch_generation.py workload) as a stream: S slots,
+    each decoding one sample at its own position; a slot whose sample ends is refilled on the device with the next
+    sample number in the same step, so all S rows stay busy until the last samples drain. The step has static
+    shapes and reads every position from the device (`pos[s]`), so it is captured once and replayed.
+
+    One step: slot_embed -> per layer (slot_splice of z_projections[i](z) into the rows at position 1, LayerNorm,
+    q|k|v slot_linear with rotary at pos-1, slot_attn, output linear, LayerNorm, FFN) -> output head ->
+    slot_penalty -> slot_sample (token into ids and into the result buffer, advance or finish) -> slot_refill ->
+    the z projections of the slots' latents for the next step. The arithmetic per row is KVDecoder's, kernel for
+    kernel (the same bodies, the same split rule through a `part` workspace of the same 16 * S * 4d floats), so
+    sample j equals row j of `sample()` on the same z and seed while the slot count stays within the same number
+    of 64-row blocks (the split rule reads the block count).
+
+    A refilled slot reuses its cache rows as they are: at position p only keys <= p are read, and each is written
+    by the sample's own earlier steps.
+    """
+
+    def __init__(self, engine, num_samples, max_length, slots, z, start_token, end_token, *, top_k=0, top_p=0.9,
+                 temperature=1.0, repetition_penalty=1.2, seed=0, use_graph=True):
+        P, hp = engine.P, engine.hp
+        self.eng, self.P = engine, P
+        dev = P.device
+        if dev.type != 'cuda':
+            raise RuntimeError('StreamDecoder runs on the MI355X kernels: pass a GPU engine (no CPU fallback)')
+        N, T, S = int(num_samples), int(max_length), int(slots)
+        if N < 1 or S < 1 or not 3 <= T <= 32768:
+            raise ValueError(f'StreamDecoder: num_samples {N}, slots {S}, max_length {T} (3..32768)')
+        d, H, NL, V = engine.d, engine.H, hp.num_layers, hp.vocab_size
+        self.N, self.T, self.S, self.d, self.H, self.hd, self.NL, self.V = N, T, S, d, H, engine.hd, NL, V
+        self.window = engine.window
+        self.start, self.end = int(start_token), int(end_token)
+        self.top_k, self.top_p, self.temperature = int(top_k), float(top_p), float(temperature)
+        self.repetition_penalty, self.seed = float(repetition_penalty), int(seed)
+        self.z_all = z.reshape(N, -1).to(dev, f32).contiguous()
+        Z = self.z_all.shape[1]
+        i32 = lambda v: torch.full((S,), v, device=dev, dtype=torch.int32)   # noqa: E731
+        self.pos, self.key = i32(-1), i32(-1)            # every slot "finished" without a sample: the first refill
+        self.next = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.completed = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.ids = torch.zeros(S, T, device=dev, dtype=torch.long)
+        self.out = torch.zeros(N, T - 1, device=dev, dtype=torch.int16)
+        z_ = lambda *s: torch.zeros(*s, device=dev, dtype=f32)   # noqa: E731  (idle rows stay finite)
+        # every layer's z projection as one [NL * d, Z] operand (a packed copy: the arena interleaves them with
+        # the layers), so the slots' latents are projected by one launch into zp [S, NL * d]; a row's dot products
+        # do not depend on how many output columns the launch has
+        self.z_slot, self.zp = z_(S, Z), z_(S, NL * d)
+        self.wz = torch.cat([P.f(f'z_projections.{i}.weight').reshape(d, Z) for i in range(NL)]).contiguous()
+        self.bz = torch.cat([P.f(f'z_projections.{i}.bias').reshape(d) for i in range(NL)]).contiguous()
+        self.kc = torch.empty(NL, S, H, T, self.hd, device=dev, dtype=f32)
+        self.vc = torch.empty_like(self.kc)
+        self.rot = engine.rot(T, self.window)
+        self.x, self.h, self.x1 = z_(S, d), z_(S, d), z_(S, d)
+        self.qkv, self.O, self.f = z_(S, 3 * d), z_(S, d), z_(S, 4 * d)
+        self.h0, self.hh, self.logits = z_(S, d), z_(S, d), z_(S, V)
+        self.part = z_(16 * S * 4 * d)
+        self.use_graph = use_graph
+        self.graph = None
+        self.steps = 0
+
+    def _layer(self, i):
+        P, S, d = self.P, self.S, self.d
+        pre = f'decoder_layers.{i}.'
+        a = pre + 'attention.'
+        x = self.x
+        K.slot_splice(x, self.zp[:, i * d:], self.pos, S, d, ldz=self.NL * d)
+        K.layernorm_fwd_f32(x, P.f(pre + 'attn_layer_norm.weight'), P.f(pre + 'attn_layer_norm.bias'), self.h, S, d)
+        K.slot_linear(self.h, P.f(a + 'q_linear.weight'), self.qkv, S, 3 * d, d, bias=P.f(a + 'q_linear.bias'),
+                      rot=self.rot, rot_cols=2 * d, rot_d=d, pos=self.pos, part=self.part)
+        K.slot_attn(self.qkv, self.kc[i], self.vc[i], self.O, S, self.H, self.hd, self.T, self.pos, self.window)
+        K.dec_linear(self.O, P.f(a + 'output_linear.weight'), self.x1, S, d, d, bias=P.f(a + 'output_linear.bias'),
+                     resid=x, part=self.part)
+        K.layernorm_fwd_f32(self.x1, P.f(pre + 'ffn_layer_norm.weight'), P.f(pre + 'ffn_layer_norm.bias'), self.h, S, d)
+        K.dec_linear(self.h, P.f(pre + 'ffn.0.weight'), self.f, S, 4 * d, d, bias=P.f(pre + 'ffn.0.bias'), epi=EPI_GELU,
+                     part=self.part)
+        K.dec_linear(self.f, P.f(pre + 'ffn.2.weight'), x, S, d, 4 * d, resid=self.x1, part=self.part)
+
+    def _refill(self):
+        """Hand finished slots their next samples, then project the slots' latents for the step that follows
+        (KVDecoder's first-step arithmetic: an un-split dec_linear, here over all layers' columns at once)."""
+        S = self.S
+        K.slot_refill(self.pos, self.key, self.ids, self.T, S, self.start, self.z_all, self.z_slot, self.N, self.next,
+                      self.completed)
+        K.dec_linear(self.z_slot, self.wz, self.zp, S, self.NL * self.d, self.z_slot.shape[1], bias=self.bz)
+
+    def _step(self):
+        P, S, d = self.P, self.S, self.d
+        K.slot_embed(self.ids, self.T, self.pos, P.f('input_layer.0.weight'), self.x, S, d)
+        for i in range(self.NL):
+            self._layer(i)
+        K.dec_linear(self.x, P.f('output_layer.0.weight'), self.h0, S, d, d, bias=P.f('output_layer.0.bias'),
+                     epi=EPI_GELU, part=self.part)
+        K.layernorm_fwd_f32(self.h0, P.f('output_layer.2.weight'), P.f('output_layer.2.bias'), self.hh, S, d)
+        K.dec_linear(self.hh, P.f('input_layer.0.weight'), self.logits, S, self.V, d, bias=P.f('output_layer.3.bias'))
+        if self.repetition_penalty > 1.0:
+            K.slot_penalty(self.logits, S, self.ids, self.T, self.pos, self.repetition_penalty)
+        K.slot_sample(self.logits, self.V, S, self.ids, self.T, self.pos, self.key, self.out, self.N, self.end,
+                      self.temperature, self.top_k, self.top_p, self.seed)
+        self._refill()
+
+    def max_steps(self):
+        """Every sample takes at most T - 2 steps and a slot is never idle while samples remain."""
+        return (-(-self.N // self.S) + 1) * (self.T - 1)
+
+    def run(self, check_every=8):
+        """Fill the slots, then step until the device has counted num_samples completed samples. The host reads
+        that counter every `check_every` steps and at no other time."""
+        self._refill()
+        bound = self.max_steps()
+        while True:
+            if self.steps % check_every == 0 or self.steps >= bound:
+                done = int(self.completed.item())
+                if done >= self.N:
+                    break
+                if self.steps >= bound:
+                    raise RuntimeError(f'StreamDecoder: {done} of {self.N} samples after {self.steps} steps '
+                                       f'(bound {bound})')
+            if self.use_graph:
+                if self.graph is None:
+                    self._capture()
+                self.graph.replay()
+            else:
+                self._step()
+            self.steps += 1
+        return self.out
+
+    def _capture(self):
+        """Capture one step. The warm-up launch advances the device state, so it is saved and restored around the
+        capture, as KVDecoder._capture does. The KV cache is not part of it: the warm-up wrote, at each slot's
+        position, the rows the first replay writes again from the same restored state."""
+        state = (self.pos, self.key, self.next, self.completed, self.ids, self.out, self.z_slot, self.zp)
+        saved = [t.clone() for t in state]
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self._step()                     # warm-up outside the graph
+        torch.cuda.current_stream().wait_stream(s)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._step()
+        for t, v in zip(state, saved):
+            t.copy_(v)
         self.graph = g

@@ -757,6 +757,84 @@ def dec_advance(cur):
     check(lib.svae_dec_advance(cur.data_ptr(), stream()), 'svae_dec_advance')
 
 
+# ---- streaming bulk sampling (f32; one position per slot: pos int32 [S], 0 = idle, < 0 = finished)
+def _slot_state(S, *ts):
+    _dev(*ts)
+    for t in ts:
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= S
+
+
+def slot_linear(X, W, Y, S, N_, K_, *, rot, rot_cols, rot_d, pos, bias=None, resid=None, ldx=None, ldw=None,
+                ldy=None, ldr=None, part=None):
+    """svae_slot_linear: dec_linear with the rotary epilogue at position pos[m]-1 of each row."""
+    _dev(X, W, Y, rot)
+    _slot_state(S, pos)
+    assert X.dtype == f32 and W.dtype == f32 and Y.dtype == f32
+    check(lib.svae_slot_linear(X.data_ptr(), ldx or K_, W.data_ptr(), ldw or K_, ptr(bias), Y.data_ptr(), ldy or N_,
+                               ptr(resid), ldr or N_, S, N_, K_, rot.data_ptr(), rot_cols, rot_d, pos.data_ptr(),
+                               ptr(part), part.numel() if part is not None else 0, stream()), 'svae_slot_linear')
+
+
+def slot_attn(qkv, kc, vc, O, S, H, hd, T, pos, window, scale=None, ldq=None, ldo=None):
+    _dev(qkv, kc, vc, O)
+    _slot_state(S, pos)
+    assert kc.numel() >= S * H * T * hd and vc.numel() >= S * H * T * hd
+    check(lib.svae_slot_attn(qkv.data_ptr(), ldq or 3 * H * hd, kc.data_ptr(), vc.data_ptr(), S, H, hd, T,
+                             pos.data_ptr(), window, hd ** -0.5 if scale is None else scale, O.data_ptr(),
+                             ldo or H * hd, stream()), 'svae_slot_attn')
+
+
+def slot_embed(ids, T, pos, table, x, S, D):
+    _dev(ids, table, x)
+    _slot_state(S, pos)
+    assert ids.dtype == torch.int64 and ids.numel() >= S * T
+    check(lib.svae_slot_embed(ids.data_ptr(), T, pos.data_ptr(), table.data_ptr(), x.data_ptr(), S, D, stream()),
+          'svae_slot_embed')
+
+
+def slot_splice(x, zp, pos, S, D, ldz=None):
+    """x[s] = zp[s][:D] for the slots at position 1; zp may be a column block of a wider [S, ldz] buffer."""
+    _dev(x, zp)
+    _slot_state(S, pos)
+    ldz = ldz or D
+    assert x.dtype == f32 and zp.dtype == f32 and x.numel() >= S * D
+    assert zp.shape == (S, zp.shape[1]) and zp.shape[1] >= D and zp.stride() == (ldz, 1)
+    check(lib.svae_slot_splice(x.data_ptr(), zp.data_ptr(), ldz, pos.data_ptr(), S, D, stream()), 'svae_slot_splice')
+
+
+def slot_penalty(logits, S, ids, T, pos, penalty):
+    _dev(logits, ids)
+    _slot_state(S, pos)
+    assert ids.dtype == torch.int64 and ids.numel() >= S * T
+    check(lib.svae_slot_penalty(logits.data_ptr(), logits.stride(0), S, ids.data_ptr(), T, pos.data_ptr(), penalty,
+                                stream()), 'svae_slot_penalty')
+
+
+def slot_sample(logits, V, S, ids, T, pos, key, out, num_samples, end_token, temperature, top_k, top_p, seed):
+    """out: int16 [num_samples, T - 1], zeroed by the caller; the token of slot s lands in out[key[s]][pos[s] - 1]."""
+    _dev(logits, ids, out)
+    _slot_state(S, pos, key)
+    assert ids.dtype == torch.int64 and ids.numel() >= S * T
+    assert out.dtype == torch.int16 and out.is_contiguous() and out.numel() >= num_samples * (T - 1)
+    check(lib.svae_slot_sample(logits.data_ptr(), logits.stride(0), V, S, ids.data_ptr(), T, pos.data_ptr(),
+                               key.data_ptr(), out.data_ptr(), num_samples, end_token, temperature, top_k, top_p,
+                               seed & 0xFFFFFFFFFFFFFFFF, stream()), 'svae_slot_sample')
+
+
+def slot_refill(pos, key, ids, T, S, start_token, z_all, z_slot, num_samples, next_sample, completed):
+    """svae_slot_refill: finished slots take the next sample numbers in slot order (or go idle)."""
+    _dev(ids, z_all, z_slot)
+    _slot_state(S, pos, key)
+    _slot_state(1, next_sample, completed)
+    Z = z_slot.shape[-1]
+    assert ids.dtype == torch.int64 and ids.numel() >= S * T
+    assert z_all.dtype == f32 and z_slot.dtype == f32 and z_all.is_contiguous() and z_slot.is_contiguous()
+    assert z_all.numel() >= num_samples * Z and z_slot.numel() >= S * Z
+    check(lib.svae_slot_refill(pos.data_ptr(), key.data_ptr(), ids.data_ptr(), T, S, start_token, z_all.data_ptr(),
+                               z_slot.data_ptr(), Z, num_samples, next_sample.data_ptr(), completed.data_ptr(),
+                               stream()), 'svae_slot_refill')
+
+
 def _latent_rows(*ts):
     """The [rows, Z] f32 operands of the latent kernels: contiguous device tensors of one shape."""
     _dev(*ts)

@@ -25,7 +25,7 @@ from .core import (ContinuousVAEHparams, ContinuousVAEHooks, ConditionalGaussian
 from .core.padded_tensor import PaddedTensor
 from .engine import FlatParams, VAEEngine
 from .core.generation import GenerationState
-from .decoding import KVDecoder
+from .decoding import KVDecoder, StreamDecoder
 from . import kernels as K
 from ._native import EPI_F32, EPI_BF16
 
@@ -467,6 +467,38 @@ class TransformerVAE(ContinuousVAEHooks, LanguageModel):
         end = self.end_token if self.end_token is not None else 2            # [SEP]
         state = GenerationState(max_length, batch_size, start, end, device=self.device, **kwargs)
         return KVDecoder(eng, state, z.to(self.device), use_graph=use_graph).run()
+
+    @torch.no_grad()
+    def sample_stream(self, max_length: int, num_samples: int, slots: Optional[int] = None, z=None,
+                      use_graph: bool = True, **kwargs):
+        """Bulk unconditional sampling (the reference's sample.py workload): `num_samples` independent samples of
+        up to max_length tokens through `slots` decoder rows, each refilled on the device with the next sample
+        as soon as its current one ends (StreamDecoder). Returns an int16 device tensor
+        [num_samples, max_length - 1]: row j is sample j (`sample`'s row j for the same z and seed), zero after
+        its end. z: [num_samples, 1, latent] (default N(0, I)); kwargs: GenerationState's top_k / top_p /
+        temperature / repetition_penalty; the seed comes from torch's default generator. slots defaults to
+        min(num_samples, 1000). None below kl_weight 1, as `sample`."""
+        if self.hparams.kl_weight < 1.0:
+            return None
+        eng = self._require_engine()
+        num_samples, max_length = int(num_samples), int(max_length)
+        if num_samples < 0 or max_length < 2:
+            raise ValueError(f'sample_stream: num_samples {num_samples}, max_length {max_length}')
+        out = torch.zeros(num_samples, max_length - 1, device=self.device, dtype=torch.int16)
+        if num_samples == 0 or max_length == 2:      # nothing to decode (sample() stops before its first step)
+            return out
+        if z is None:
+            z = torch.randn(num_samples, 1, self.hparams.latent_depth, device=self.device)
+        if z.shape[0] != num_samples:
+            raise ValueError(f'sample_stream: z has {z.shape[0]} rows for {num_samples} samples')
+        slots = min(num_samples, 1000) if slots is None else int(slots)
+        start = self.start_token if self.start_token is not None else 1      # [CLS] (text_data_module.py:271)
+        end = self.end_token if self.end_token is not None else 2            # [SEP]
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())                   # as GenerationState.__post_init__
+        dec = StreamDecoder(eng, num_samples, max_length, slots, z, start, end, seed=seed, use_graph=use_graph, **kwargs)
+        out = dec.run()
+        self.last_stream_steps = dec.steps                                   # for scripts/bench_sample.py
+        return out
 
     @torch.no_grad()
     def embed(self, ids):
