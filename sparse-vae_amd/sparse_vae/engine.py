@@ -192,26 +192,17 @@ class FlatParams:
 
 # ---------------------------------------------------------------------------------------- workspace
 class Workspace:
-    """Named device buffers reused across steps. A buffer still being read by the weight-gradient stream is
-    fenced: get() makes the caller's stream wait for that read before handing the buffer out again."""
+    """Named device buffers reused across steps."""
 
     def __init__(self, device):
         self.device = device
         self.bufs = {}
-        self.busy = {}      # storage data_ptr -> event recorded after the last side-stream read
-
-    def fence(self, t):
-        ev = self.busy.pop(t.untyped_storage().data_ptr(), None)
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)
 
     def get(self, name, shape, dtype=bf16, zero=False):
         t = self.bufs.get(name)
         if t is None or t.shape != torch.Size(shape) or t.dtype != dtype:
             t = torch.empty(shape, dtype=dtype, device=self.device)
             self.bufs[name] = t
-        if self.busy:
-            self.fence(t)
         if zero:
             t.zero_()
         return t
@@ -250,65 +241,28 @@ class VAEEngine:
         self.window = getattr(hp, 'attn_window', 0)     # decoder self-attention: 0 dense, > 0 sliding window
         self.saved = None
         self.probe = None      # list -> HIP events around each vocab-head GEMM launch (bench roofline)
-        # SVAE_DW_STREAM=1: weight-gradient GEMMs on a second stream, off the dX critical path of the backward
-        # (they feed nothing else in it). Measured at C2: 15.33 vs 15.37 ms/step -- the overlap is eaten by
-        # contention (LayerNorm backward 35 -> 85 us beside a GEMM, the head dW doubled beside the head dX), so
-        # the default keeps one stream.
         # vocabulary head + cross entropy of the training step: 'prob' stores P = exp(logit - label logit) and runs
         # the backward on it without a dlogits pass (svae.h, P-head); 'logits' stores the bf16 logits and rewrites
         # them into dlogits in place (ce_grad) -- the round-1 path, kept for A/B runs (SVAE_HEAD=logits)
         self.head_mode = os.environ.get('SVAE_HEAD', 'prob')
         assert self.head_mode in ('prob', 'logits'), self.head_mode
-        # the two dW GEMMs of the FFN, and the attention output projection's with the Q/K/V projection's, run as one
-        # paired launch each (kernels.linear_dw_pair); SVAE_DW_PAIR=0 launches them one by one (A/B runs)
-        self.dw_pair = os.environ.get('SVAE_DW_PAIR', '1') != '0'
         # every layer's weight-gradient GEMMs deferred to one grouped pass at the end of the backward
         # (kernels.linear_dw_group: the chip filled across layers instead of across K; the layers' dY buffers are then
         # per-layer workspace). Not with data-parallel hooks (the bucketed all-reduce needs the gradients in ready
-        # order) or the side stream; SVAE_DW_GROUP=0 restores the per-layer launches (A/B runs)
+        # order); SVAE_DW_GROUP=0 restores the per-layer launches (A/B runs), where the two dW GEMMs of the FFN, and
+        # the attention output projection's with the Q/K/V projection's, run as one paired launch each
+        # (kernels.linear_dw_pair)
         self.dw_group = os.environ.get('SVAE_DW_GROUP', '1') != '0'
         self._dw_jobs = []          # the deferred jobs of this backward
         self._dwq = None            # = _dw_jobs while a layer_bwd records into it (else None: _dw launches in place)
         self._dw_names = False      # this backward keeps the layers' dY operands in per-layer buffers
         self._dwg_states, self._dwg_sched = [], {}
-        # decoder residual adds in a separate fused residual + dropout + LayerNorm pass (layer_fwd's fuse, SVAE_FUSE_LN=1)
-        # instead of the projections' f32 residual epilogues + LayerNorm passes. Off by default: measured at C2 it moves
-        # 36 B per element and layer against 28 (the projection output makes an f32 round trip), +0.125 ms of kernel
-        # time per step (profiles/r03f_*); at C4 +0.5-0.8 ms/step
-        self.fuse_ln = os.environ.get('SVAE_FUSE_LN', '0') != '0'
-        # attention backward delta = rowsum(dO . O): SVAE_DELTA_FUSED=1 has the dO GEMM's epilogue write it (built and
-        # tested, measured no faster: C2 12.725 / 12.696 vs 12.648 / 12.681 ms, C4 neutral,
-        # profiles/r04j_delta_ab.log); default: the attention backward's own delta pass
-        self.delta_fused = os.environ.get('SVAE_DELTA_FUSED', '0') != '0'
-        # the attention forward's copy of O for the backward's delta: the bf16 residual O - bf16(O) (2 B per element)
-        # unless SVAE_ATTN_O32=1 (the f32 copy, 4 B; A/B runs)
-        self.o32_mode = os.environ.get('SVAE_ATTN_O32', '0') != '0'
-        # the last decoder layer's dropout + residual GEMM epilogue also writes the bf16 copy of its output (the vocab
-        # head's input) instead of a separate [T, d] cast pass; SVAE_RESID_BF16=0 restores the cast (A/B runs)
-        self.resid_bf16 = os.environ.get('SVAE_RESID_BF16', '1') != '0'
-        # and the head's d x GEMM writes the top decoder layer's dropout-masked bf16 gradient (SVAE_HEAD_G2=0: the
-        # layer backward's own dropout_bwd_cast pass)
-        self.head_g2 = os.environ.get('SVAE_HEAD_G2', '1') != '0'
-        # the head LayerNorm's backward writes bf16(dx * GELU') directly (SVAE_LN_GELU=0: f32 dx + a gelu_bwd pass)
-        self.ln_gelu = os.environ.get('SVAE_LN_GELU', '1') != '0'
-        # the step's token inputs (ids32, labels, padding mask, token counts) and its scalars (loss, gradient scales)
-        # in one launch each instead of torch's copy / fill / mul / add ops (SVAE_SMALL_FUSED=0: the torch ops)
-        self.small_fused = os.environ.get('SVAE_SMALL_FUSED', '1') != '0'
-        # the decoder layers' z-projection backwards in one launch (SVAE_ZPROJ_BATCH=0: one launch per layer)
-        self.zp_batch = os.environ.get('SVAE_ZPROJ_BATCH', '1') != '0'
-        # and their forwards (one launch; each layer's first LayerNorm splices its rows in; SVAE_ZPROJ_FWD_BATCH=0: a
-        # skinny GEMM per layer into the position-0 rows)
-        self.zf_batch = os.environ.get('SVAE_ZPROJ_FWD_BATCH', '1') != '0'
+        # the decoder layers' z-projection backwards wait here for one launch (flush_zproj), the LayerNorm-affine
+        # gradient partials of consecutive LayerNorm backwards for one summing launch (flush_colsum)
         self._zp_pending, self._zp_ctx = [], None
-        # the LayerNorm-affine gradient partials of consecutive LayerNorm backwards summed in one launch
-        # (SVAE_COLSUM_BATCH=0: one colsum launch per LayerNorm, for A/B runs)
-        self.cs_batch = os.environ.get('SVAE_COLSUM_BATCH', '1') != '0'
         self._cs_pending = []
         self.ncu = (torch.cuda.get_device_properties(flat.device).multi_processor_count
                     if flat.device.type == 'cuda' else 256)
-        self.side = None
-        if flat.device.type == 'cuda' and os.environ.get('SVAE_DW_STREAM', '0') != '0':
-            self.side = torch.cuda.Stream(device=flat.device)
 
     # ------------------------------------------------------------------ helpers
     def rot(self, L, window=0):
@@ -340,14 +294,6 @@ class VAEEngine:
         x, mean, rstd = st
         D = self.d
         wg = self.P.grad[self.P.offsets[name + '.weight'][0]:][:2 * D]   # [weight | bias] grads (adjacent)
-        if not self.cs_batch:
-            part = self.ws.get('ln.part', (1024 * 2 * D,), f32)
-            if gelu is not None:
-                K.layernorm_bwd_gelu(dy, x, self.P.f(name + '.weight'), mean, rstd, gelu, dx_bf, wg, rows, D, part)
-                return
-            K.layernorm_bwd(dy, x, self.P.f(name + '.weight'), mean, rstd, dres, dx, dx_bf, wg, rows, D, part,
-                            bf_drop=bf_drop, zsplice=zsplice)
-            return
         # the affine-gradient partials wait in their own slice of the workspace; flush_colsum sums up to
         # COLSUM_MAX of them in one launch (at every ready() point and at the end of the backward)
         if len(self._cs_pending) == COLSUM_MAX:
@@ -374,24 +320,21 @@ class VAEEngine:
             K.colsum_multi(self._cs_pending)
             self._cs_pending = []
 
-    def _dw(self, dY, X, wname, rows, n_out, n_in, ldy=None, ldx=None, bias=None, on_side=True):
+    def _job(self, dY, X, wname, rows, n_out, n_in, ldy=None, ldx=None, bias=None):
+        """The weight-gradient job (kernels.DwJob) of a linear layer, by parameter names: grad(wname)[n_out, n_in] +=
+        dY^T . X over rows, and with bias, grad(bias)[:n_out] += column sums of dY."""
         bg = None
         if bias is not None:
             off = self.P.offsets[bias][0]
             bg = self.P.grad[off:off + n_out]
-        side = self.side if on_side else None
-        if self._dwq is not None and on_side and rows >= K.GROUP_MIN_ROWS:
-            self._dwq.append((dY, X, self.P.g(wname), rows, n_out, n_in, ldy, ldx, bg))
-            return
-        if side is None:
-            K.linear_dw(dY, X, self.P.g(wname), rows, n_out, n_in, ldy, ldx, bgrad=bg)
-            return
-        side.wait_stream(torch.cuda.current_stream())       # dY (and X) are written
-        with torch.cuda.stream(side):
-            K.linear_dw(dY, X, self.P.g(wname), rows, n_out, n_in, ldy, ldx, bgrad=bg)
-        ev = torch.cuda.Event()
-        ev.record(side)
-        self.ws.busy[dY.untyped_storage().data_ptr()] = ev   # the next writer of dY's buffer waits for this read
+        return K.DwJob(dY, X, self.P.g(wname), rows, n_out, n_in, ldy, ldx, bg)
+
+    def _dw(self, job):
+        """Launch a weight-gradient job, or record it for the grouped pass while a layer_bwd defers them."""
+        if self._dwq is not None and job.rows >= K.GROUP_MIN_ROWS:
+            self._dwq.append(job)
+        else:
+            K.linear_dw(*job)
 
     def _head_dw_splits(self, V, d):
         """Split-K factor of the vocabulary head's dW (M = V, N = d, K = T): 2 when one split leaves the last wave of
@@ -406,22 +349,12 @@ class VAEEngine:
         return 2 if tiles >= ncu and eff(2) > eff(1) + 0.1 else 1
 
     def _dw_pair(self, j0, j1):
-        """Two _dw's ((dY, X, wname, rows, n_out, n_in[, ldy, ldx, bias])) in one paired launch (svae_gemm_pair):
-        half the split-K slab traffic of two separate launches. SVAE_DW_PAIR=0 (or the side stream) runs them apart."""
-        if self._dwq is not None or self.side is not None or not self.dw_pair:
-            for j in (j0, j1):
-                self._dw(*j[:6], *(tuple(j[6:]) + (None,) * (9 - len(j))))
-            return
-        args = []
-        for j in (j0, j1):
-            dY, X, wname, rows, n_out, n_in = j[:6]
-            ldy, ldx, bias = tuple(j[6:]) + (None,) * (9 - len(j))
-            bg = None
-            if bias is not None:
-                off = self.P.offsets[bias][0]
-                bg = self.P.grad[off:off + n_out]
-            args.append((dY, X, self.P.g(wname), rows, n_out, n_in, ldy, ldx, bg))
-        K.linear_dw_pair(*args)
+        """Two _dw's in one paired launch (svae_gemm_pair): half the split-K slab traffic of two separate launches."""
+        if self._dwq is not None:
+            self._dw(j0)
+            self._dw(j1)
+        else:
+            K.linear_dw_pair(j0, j1)
 
     def _bname(self, name, st):
         """Workspace name of a layer_bwd buffer a weight-gradient GEMM reads: per layer while those GEMMs are deferred
@@ -434,7 +367,7 @@ class VAEEngine:
         k = 0   # each call of the schedule keeps its own parameter table (unchanged from step to step)
         for c in range(0, len(q), GROUP_MAX):
             jobs = q[c:c + GROUP_MAX]
-            key = tuple((j[4], j[5], j[3]) for j in jobs)
+            key = tuple((j.n_out, j.n_in, j.rows) for j in jobs)
             if key not in self._dwg_sched:
                 self._dwg_sched[key] = K.group_schedule(key, self.ncu)
             for idx, splits, slab in self._dwg_sched[key]:
@@ -443,42 +376,27 @@ class VAEEngine:
                 K.linear_dw_group([jobs[i] for i in idx], splits, self._dwg_states[k], slab=slab)
                 k += 1
 
-    def join_side(self):
-        """The caller's stream waits for every weight-gradient GEMM issued so far."""
-        if self.side is not None:
-            torch.cuda.current_stream().wait_stream(self.side)
-            self.ws.busy.clear()
-
     def _db(self, dY, bname, rows, cols, ld=None):
         off = self.P.offsets[bname][0]
         K.colsum(dY, rows, cols, ld or cols, self.P.grad[off:off + cols])
 
     # ------------------------------------------------------------------ one transformer layer
     def layer_fwd(self, pre, x, B, Sx, L, pad, *, learned=0, cross=False, causal=False, ctx=None, heads, hd,
-                  drop_p=0.0, seed=0, tag, out=None, window=0, fuse=False, h_in=None, next_ln=None, out_bf=None,
-                  zsplice=None, ctx_ln=None):
+                  drop_p=0.0, seed=0, tag, out=None, window=0, out_bf=None, zsplice=None, ctx_ln=None):
         """TransformerLayer.forward (transformer_layer.py:44-61) on x f32 [B*Sx, d]. Returns the f32 output
         [B*Lq, d] and the saved state for layer_bwd. window > 0: sliding-window self-attention.
 
-        fuse (no cross-attention): the two residual adds run in the fused residual + dropout + LayerNorm pass
-        (svae_resid_ln_fwd) instead of the projection GEMMs' f32 epilogues -- the out-projection writes bf16 and the
-        pass makes x1 = x + y and LayerNorm_f(x1); the FFN output is added (with its dropout) by the same pass fused
-        with the NEXT layer's attention LayerNorm: next_ln = (LayerNorm name, z rows [B, d] f32, L, next tag) -- the z
-        splice's rows are taken from the z rows -- which leaves (h, (x, mean, rstd)) in st['next_h'] for the next
-        layer's h_in; without next_ln (the last layer) only the bf16 copy of the output is written, into out_bf (the
-        head's input). ctx_ln = (cx, (ctx, mean, rstd)): this layer's context LayerNorm output, computed by the batched
-        pass (ctx_ln_batched); its backward is then left to the caller (st['ctx_deferred'])."""
+        zsplice = (z rows f32 [B, d], Sx): the position-0 rows of x come from the batched z projections
+        (svae_layernorm_fwd_z); out_bf: the FFN-output epilogue also writes the bf16 copy of the output (the vocabulary
+        head's input, last decoder layer). ctx_ln = (cx, (ctx, mean, rstd)): this layer's context LayerNorm output,
+        computed by the batched pass (ctx_ln_batched); its backward is then left to the caller (st['ctx_deferred'])."""
         d, ws, P = self.d, self.ws, self.P
         rows_x = B * Sx
         rot = self.rot(max(Sx, L), window)
         st = {'pre': pre, 'B': B, 'Sx': Sx, 'L': L, 'learned': learned, 'cross': cross, 'causal': causal,
               'heads': heads, 'hd': hd, 'drop_p': drop_p, 'seed': seed, 'x': x, 'tag': tag, 'window': window}
         a = pre + 'attention.'
-        fuse = fuse and not cross
-        if h_in is not None:
-            h, st['ln_a'] = h_in
-        else:   # (zsplice: the position-0 rows of x come from the batched z projections, svae_layernorm_fwd_z)
-            h, st['ln_a'] = self._ln_fwd(pre + 'attn_layer_norm', x, rows_x, tag + '.ln_a', zsplice=zsplice)
+        h, st['ln_a'] = self._ln_fwd(pre + 'attn_layer_norm', x, rows_x, tag + '.ln_a', zsplice=zsplice)
         st['h'] = h
         pad_k = pad if Sx == L else None          # PaddedTensor getter: mask iff key length == L
         if learned:
@@ -508,20 +426,8 @@ class VAEEngine:
         st.update(O=O, Ox=Ox, lse=lse, Lq=Lq, pad_k=pad_k)
         resid = Lq == Sx                           # transformer_layer.py:49
         x1 = ws.get(tag + '.x1', (rows_q, d), f32)
-        if fuse:
-            # (the projection output stays f32: rounded to bf16 before the residual add it moved the C5-shape bottleneck
-            # key gradient -- a cancellation residual -- past its 2 % parity bar)
-            ya = ws.get('fuse.y', (rows_q, d), f32)
-            K.gemm(O, P.w(a + 'output_linear.weight'), ya, rows_q, d, d, epi=EPI_F32, bias=P.f(a + 'output_linear.bias'))
-            nm = pre + 'ffn_layer_norm'
-            h2 = ws.get(tag + '.ln_f.y', (rows_q, d))
-            mf, rf = ws.get(tag + '.ln_f.mean', (rows_q,), f32), ws.get(tag + '.ln_f.rstd', (rows_q,), f32)
-            K.resid_ln_fwd(x if resid else None, ya, h2, rows_q, d, w=P.f(nm + '.weight'), b=P.f(nm + '.bias'), mean=mf,
-                           rstd=rf, xo=x1)
-            st['ln_f'] = (x1, mf, rf)
-        else:
-            K.gemm(O, P.w(a + 'output_linear.weight'), x1, rows_q, d, d, epi=EPI_F32,
-                   bias=P.f(a + 'output_linear.bias'), resid=x if resid else None, ldr=d)
+        K.gemm(O, P.w(a + 'output_linear.weight'), x1, rows_q, d, d, epi=EPI_F32,
+               bias=P.f(a + 'output_linear.bias'), resid=x if resid else None, ldr=d)
         st['resid'] = resid
         st['x1'] = x1
         xc = x1
@@ -551,40 +457,20 @@ class VAEEngine:
                    bias=P.f(c + 'output_linear.bias'), resid=x1, ldr=d)
             st.update(cx=cx, hq=hq, qc=qc, kvc=kvc, Oc=Oc, lsec=lsec, x2=x2, pad_ctx=pad)
             xc = x2
-        if not fuse:
-            h2, st['ln_f'] = self._ln_fwd(pre + 'ffn_layer_norm', xc, rows_q, tag + '.ln_f')
+        h2, st['ln_f'] = self._ln_fwd(pre + 'ffn_layer_norm', xc, rows_q, tag + '.ln_f')
         gprime = ws.get(tag + '.gprime', (rows_q, 4 * d))   # gelu'(pre-activation), saved by the epilogue
         f = ws.get(tag + '.f', (rows_q, 4 * d))
         K.gemm(h2, P.w(pre + 'ffn.0.weight'), f, rows_q, 4 * d, d, epi=EPI_GELU, bias=P.f(pre + 'ffn.0.bias'),
                aux=gprime, ldaux=4 * d)
-        if fuse:
-            yf = ws.get('fuse.y', (rows_q, d), f32)
-            K.gemm(f, P.w(pre + 'ffn.2.weight'), yf, rows_q, d, 4 * d, epi=EPI_F32)
-            if next_ln is not None:
-                nm, zrows, zmod, ntag = next_ln
-                out = ws.get(tag + '.out', (rows_q, d), f32) if out is None else out
-                hn = ws.get(ntag + '.ln_a.y', (rows_q, d))
-                mn, rn = ws.get(ntag + '.ln_a.mean', (rows_q,), f32), ws.get(ntag + '.ln_a.rstd', (rows_q,), f32)
-                K.resid_ln_fwd(xc, yf, hn, rows_q, d, w=P.f(nm + '.weight'), b=P.f(nm + '.bias'), mean=mn, rstd=rn,
-                               xo=out, drop_p=drop_p, seed=seed, zrows=zrows, zmod=zmod)
-                st['next_h'] = (hn, (out, mn, rn))
-            else:
-                assert out_bf is not None, 'the last fused layer writes the bf16 copy of its output'
-                K.resid_ln_fwd(xc, yf, out_bf, rows_q, d, xo=out, drop_p=drop_p, seed=seed)
-        else:
-            out = ws.get(tag + '.out', (rows_q, d), f32) if out is None else out
-            # (out_bf: the last decoder layer's epilogue also writes the bf16 copy the vocabulary head reads)
-            K.gemm(f, P.w(pre + 'ffn.2.weight'), out, rows_q, d, 4 * d, epi=EPI_DROPOUT_RESID, resid=xc, ldr=d,
-                   drop_p=drop_p, seed=seed, aux=out_bf, ldaux=d if out_bf is not None else 0)
+        out = ws.get(tag + '.out', (rows_q, d), f32) if out is None else out
+        K.gemm(f, P.w(pre + 'ffn.2.weight'), out, rows_q, d, 4 * d, epi=EPI_DROPOUT_RESID, resid=xc, ldr=d,
+               drop_p=drop_p, seed=seed, aux=out_bf, ldaux=d if out_bf is not None else 0)
         st.update(h2=h2, gprime=gprime, f=f, xc=xc, rows_q=rows_q)
         return out, st
 
     def _o_extra(self, tag, rows_q, d, Lq):
         """The forward's extra copy of O for the backward's delta = rowsum(dO . O): the bf16 residual O - bf16(O)
-        (o_lo, 2 B per element) by default; the f32 copy (o32) where the dO GEMM's delta epilogue reads it
-        (SVAE_DELTA_FUSED=1) or SVAE_ATTN_O32=1. Keyword arguments for kernels.attention."""
-        if self.delta_fused or self.o32_mode:
-            return dict(o32=self.ws.get(tag + '32', (rows_q, d), f32), so32=d, bo32=Lq * d)
+        (o_lo, 2 B per element). Keyword arguments for kernels.attention."""
         return dict(o_lo=self.ws.get(tag + 'lo', (rows_q, d)), so_lo=d, bo_lo=Lq * d)
 
     def _dq_part(self, B, H, Lq, Lk, hd, window=0):
@@ -620,8 +506,8 @@ class VAEEngine:
         K.gemm(g2, P.wT(pre + 'ffn.2.weight', d, 4 * d), dpre, rows_q, 4 * d, d, epi=EPI_GELU_BWD, aux=st['gprime'],
                ldaux=4 * d)
         # (g2 stays intact until the next layer's backward)
-        self._dw_pair((g2, st['f'], pre + 'ffn.2.weight', rows_q, d, 4 * d),
-                      (dpre, st['h2'], pre + 'ffn.0.weight', rows_q, 4 * d, d, None, None, pre + 'ffn.0.bias'))
+        self._dw_pair(self._job(g2, st['f'], pre + 'ffn.2.weight', rows_q, d, 4 * d),
+                      self._job(dpre, st['h2'], pre + 'ffn.0.weight', rows_q, 4 * d, d, bias=pre + 'ffn.0.bias'))
         dh2 = ws.get('b.dh2', (rows_q, d))
         K.gemm(dpre, P.wT(pre + 'ffn.0.weight', 4 * d, d), dh2, rows_q, d, 4 * d, epi=EPI_BF16)
         dxc = ws.get('b.dxc', (rows_q, d), f32)
@@ -633,23 +519,20 @@ class VAEEngine:
             rows_c = B * L
             dOc = ws.get('b.dO', (rows_q, d))
             delta = ws.get('b.delta', (B, heads, Lq), f32)
-            # the dO GEMM also writes delta = rowsum(dO . O) per head (its epilogue holds dO; no separate pass)
-            K.gemm(gxc, P.wT(c + 'output_linear.weight', d, d), dOc, rows_q, d, d, epi=EPI_BF16, delta=delta if self.delta_fused else None,
-                   delta_o32=st['Ocx'].get('o32'), ld_o32=d, delta_hd=hd, delta_seq=Lq)
+            K.gemm(gxc, P.wT(c + 'output_linear.weight', d, d), dOc, rows_q, d, d, epi=EPI_BF16)
             dqc = ws.get(bn('b.dqc'), (rows_q, d))
             dkvc = ws.get(bn('b.dkvc'), (rows_c, 2 * d))
             K.attention(st['qc'], st['kvc'], st['kvc'][:, d:], st['Oc'], st['lsec'], B=B, H=heads, Lq=Lq, Lk=L,
                         hd=hd, sq=d, bq=Lq * d, sk=2 * d, sv=2 * d, bk=L * 2 * d, bv=L * 2 * d, so=d, bo=Lq * d,
-                        key_pad=st['pad_ctx'], causal=False, backward=True, delta_ready=self.delta_fused,
-                        dout=dOc, sdo=d, bdo=Lq * d, delta=delta, dq_bf=dqc, ldq_bf=d, dk=dkvc, dv=dkvc[:, d:],
-                        sdk=2 * d, sdv=2 * d, bdk=L * 2 * d, bdv=L * 2 * d, rot=rot, rot_d=d, **st['Ocx'],
-                        dq_part=self._dq_part(B, heads, Lq, L, hd))
-            self._dw_pair((gxc, st['Oc'], c + 'output_linear.weight', rows_q, d, d, None, None,
-                           c + 'output_linear.bias'),
-                          (dqc, st['hq'], c + 'q_linear.weight', rows_q, d, d, None, None, c + 'q_linear.bias'))
+                        key_pad=st['pad_ctx'], causal=False, backward=True, dout=dOc, sdo=d, bdo=Lq * d, delta=delta,
+                        dq_bf=dqc, ldq_bf=d, dk=dkvc, dv=dkvc[:, d:], sdk=2 * d, sdv=2 * d, bdk=L * 2 * d,
+                        bdv=L * 2 * d, rot=rot, rot_d=d, **st['Ocx'], dq_part=self._dq_part(B, heads, Lq, L, hd))
+            self._dw_pair(self._job(gxc, st['Oc'], c + 'output_linear.weight', rows_q, d, d,
+                                    bias=c + 'output_linear.bias'),
+                          self._job(dqc, st['hq'], c + 'q_linear.weight', rows_q, d, d, bias=c + 'q_linear.bias'))
             dhq = ws.get('b.dhq', (rows_q, d))
             K.gemm(dqc, P.wT(c + 'q_linear.weight', d, d), dhq, rows_q, d, d, epi=EPI_BF16)
-            self._dw(dkvc, st['cx'], c + 'k_linear.weight', rows_c, 2 * d, d, bias=c + 'k_linear.bias')
+            self._dw(self._job(dkvc, st['cx'], c + 'k_linear.weight', rows_c, 2 * d, d, bias=c + 'k_linear.bias'))
             # (a deferred context LayerNorm: its own gradient buffer, read by the batched backward after the layers)
             dcx = ws.get('b.dcx.' + st['tag'] if st.get('ctx_deferred') else 'b.dcx', (rows_c, d))
             K.gemm(dkvc, P.wT(c + 'k_linear.weight', 2 * d, d), dcx, rows_c, d, 2 * d, epi=EPI_BF16)
@@ -661,11 +544,10 @@ class VAEEngine:
             else:
                 self._ln_bwd(pre + 'context_layer_norm', dcx, st['ln_ctx'], rows_c, dctx, dctx)
         # ---- self / learned-query attention (attention.py:51-105)
-        wo_dw = (gx1, st['O'], a + 'output_linear.weight', rows_q, d, d, None, None, a + 'output_linear.bias')
+        wo_dw = self._job(gx1, st['O'], a + 'output_linear.weight', rows_q, d, d, bias=a + 'output_linear.bias')
         dO = ws.get('b.dO', (rows_q, d))
         delta = ws.get('b.delta', (B, heads, Lq), f32)
-        K.gemm(gx1, P.wT(a + 'output_linear.weight', d, d), dO, rows_q, d, d, epi=EPI_BF16, delta=delta if self.delta_fused else None,
-               delta_o32=st['Ox'].get('o32'), ld_o32=d, delta_hd=hd, delta_seq=Lq)
+        K.gemm(gx1, P.wT(a + 'output_linear.weight', d, d), dO, rows_q, d, d, epi=EPI_BF16)
         if st['learned']:
             kv = st['kv']
             dq32 = ws.get('b.dq32', (B * Lq, d), f32)
@@ -673,12 +555,12 @@ class VAEEngine:
             K.attention(P.w(a + 'learned_queries').view(Lq, d), kv, kv[:, d:], st['O'], st['lse'], B=B, H=heads,
                         Lq=Lq, Lk=Sx, hd=hd, sq=d, bq=0, sk=2 * d, sv=2 * d, bk=Sx * 2 * d, bv=Sx * 2 * d, so=d,
                         bo=Lq * d, key_pad=st['pad_k'], causal=False, backward=True, dout=dO, sdo=d, bdo=Lq * d,
-                        delta=delta, delta_ready=self.delta_fused, dq=dq32, bdq=Lq * d, dk=dkv, dv=dkv[:, d:], sdk=2 * d, sdv=2 * d,
+                        delta=delta, dq=dq32, bdq=Lq * d, dk=dkv, dv=dkv[:, d:], sdk=2 * d, sdv=2 * d,
                         bdk=Sx * 2 * d, bdv=Sx * 2 * d, rot=rot, rot_d=d, **st['Ox'],
                         dq_part=self._dq_part(B, heads, Lq, Sx, hd))
             K.colsum(dq32, B, Lq * d, Lq * d, P.g(a + 'learned_queries').view(-1))
-            self._dw_pair(wo_dw, (dkv, st['h'], a + 'k_linear.weight', rows_x, 2 * d, d, None, None,
-                                  a + 'k_linear.bias'))
+            self._dw_pair(wo_dw, self._job(dkv, st['h'], a + 'k_linear.weight', rows_x, 2 * d, d,
+                                           bias=a + 'k_linear.bias'))
             dh = ws.get('b.dh', (rows_x, d))
             K.gemm(dkv, P.wT(a + 'k_linear.weight', 2 * d, d), dh, rows_x, d, 2 * d, epi=EPI_BF16)
         else:
@@ -687,12 +569,11 @@ class VAEEngine:
             K.attention(qkv, qkv[:, d:], qkv[:, 2 * d:], st['O'], st['lse'], B=B, H=heads, Lq=Lq, Lk=Sx, hd=hd,
                         sq=3 * d, bq=Sx * 3 * d, sk=3 * d, sv=3 * d, bk=Sx * 3 * d, bv=Sx * 3 * d, so=d, bo=Lq * d,
                         key_pad=st['pad_k'], causal=st['causal'], window=st['window'], backward=True, dout=dO,
-                        sdo=d, bdo=Lq * d,
-                        delta=delta, delta_ready=self.delta_fused, dq_bf=dqkv, ldq_bf=3 * d, dk=dqkv[:, d:], dv=dqkv[:, 2 * d:], sdk=3 * d,
-                        sdv=3 * d, bdk=Sx * 3 * d, bdv=Sx * 3 * d, rot=rot, rot_d=d, **st['Ox'],
+                        sdo=d, bdo=Lq * d, delta=delta, dq_bf=dqkv, ldq_bf=3 * d, dk=dqkv[:, d:], dv=dqkv[:, 2 * d:],
+                        sdk=3 * d, sdv=3 * d, bdk=Sx * 3 * d, bdv=Sx * 3 * d, rot=rot, rot_d=d, **st['Ox'],
                         dq_part=self._dq_part(B, heads, Lq, Sx, hd, st['window']))
-            self._dw_pair(wo_dw, (dqkv, st['h'], a + 'q_linear.weight', rows_x, 3 * d, d, None, None,
-                                  a + 'q_linear.bias'))
+            self._dw_pair(wo_dw, self._job(dqkv, st['h'], a + 'q_linear.weight', rows_x, 3 * d, d,
+                                           bias=a + 'q_linear.bias'))
             dh = ws.get('b.dh', (rows_x, d))
             K.gemm(dqkv, P.wT(a + 'q_linear.weight', 3 * d, d), dh, rows_x, d, 3 * d, epi=EPI_BF16)
         if st['resid']:
@@ -722,15 +603,13 @@ class VAEEngine:
             padm = ws.get('pad', (B, L), torch.uint8)
         labels = ws.get('labels', (B, L), torch.int32)
         ntok64 = ws.get('ntok', (B,), torch.int64)
-        if (self.small_fused and ids.dtype == torch.int64 and ids.is_contiguous() and isinstance(ntok, torch.Tensor) and ntok.is_cuda
+        if (ids.dtype == torch.int64 and ids.is_contiguous() and isinstance(ntok, torch.Tensor) and ntok.is_cuda
                 and ntok.dtype == torch.int64 and ntok.is_contiguous() and ntok.numel() == B
                 and (padm is None or pad is True or (pad.dtype == torch.bool and pad.is_contiguous()))):
             # ids32, the next-token labels, the padding mask and the token counts in one launch
             K.prep_tokens(ids, pad if padm is not None else None, B, L, ids32, labels, padm, ntok, ntok64)
-        else:
-            ids32.copy_(ids)
-            if padm is not None:
-                padm.copy_(ids.eq(0) if pad is True else pad)
+        else:   # (other dtypes / strides: torch's copies)
+            ids32, padm = self._inputs(ids, pad)
             labels[:, :-1].copy_(ids32[:, 1:])
             labels[:, -1] = 0
             ntok64.copy_(ntok)
@@ -759,11 +638,7 @@ class VAEEngine:
         xf, sv['dec_layers'] = self._decode(x_emb, zb, padm, B, L, dropout, seed, x_ready=True)
 
         # ---- output head + cross entropy (transformer_language_model.py:55-63, language_model.py:161-170)
-        gp0 = ws.get('h0_gprime', (T, d))
-        h0 = ws.get('h0', (T, d))
-        K.gemm(xf, P.w('output_layer.0.weight'), h0, T, d, d, epi=EPI_GELU, bias=P.f('output_layer.0.bias'),
-               aux=gp0, ldaux=d)
-        hh, ln_h = self._ln_fwd('output_layer.2', h0, T, 'head.ln')
+        hh, gp0, h0, ln_h = self._head_hidden(xf, T)
         nchunks, chunk_len = K.ce_chunking(B, L, V, CE_CHUNK_NUMEL)
         lse = ws.get('ce.lse', (T,), f32)
         row_loss = ws.get('ce.row_loss', (T,), f32)
@@ -802,14 +677,10 @@ class VAEEngine:
         sv.update(xf=xf, gp0=gp0, h0=h0, hh=hh, ln_h=ln_h, logits=logits, lse=lse, chunk_w=chunk_w,
                   nchunks=nchunks, chunk_len=chunk_len, labels=labels, ids32=ids32, ntok=ntok64, x_emb=x_emb,
                   row_loss=row_loss, head=head, coff=coff)
-        if self.small_fused:
-            lbuf = ws.get('loss', (1,), f32)
-            K.step_scalars(kl_weight, nll=nll, kl=kl, loss=lbuf)                  # transformer_vae.py:55
-            loss = lbuf[0]
-        else:
-            loss = nll[0] + kl_weight * kl[0]
+        loss = ws.get('loss', (1,), f32)
+        K.step_scalars(kl_weight, nll=nll, kl=kl, loss=loss)                  # transformer_vae.py:55
         self.saved = sv
-        return {'loss': loss, 'nll': nll[0], 'kl': kl[0], 'train_kl': kl[1], 'raw_kl': raw_kl,
+        return {'loss': loss[0], 'nll': nll[0], 'kl': kl[0], 'train_kl': kl[1], 'raw_kl': raw_kl,
                 'mu': stats[:, :Z], 'logvar': stats[:, Z:], 'stats': stats, 'kl_buf': kl, 'z': zf, 'eps': eps_buf,
                 'logits': logits if need_logits else None,
                 'ce_saturated': sat[0] if head == 'prob' else None}
@@ -876,17 +747,12 @@ class VAEEngine:
             names = [g['pre'] + 'context_layer_norm' for g in grp]
             wgs = [P.grad[P.offsets[n + '.weight'][0]:][:2 * D] for n in names]
             n1 = 1024 * 2 * D
-            if self.cs_batch:
-                if len(self._cs_pending) + len(grp) > COLSUM_MAX:
-                    self.flush_colsum()
-                k = len(self._cs_pending)
-                part = self.ws.get('ln.parts', (COLSUM_MAX * n1,), f32)[k * n1:(k + len(grp)) * n1]
-                defer = self._cs_pending
-            else:
-                part = self.ws.get('ln.partm', (LN_MULTI_MAX * n1,), f32)
-                defer = None
+            if len(self._cs_pending) + len(grp) > COLSUM_MAX:
+                self.flush_colsum()
+            k = len(self._cs_pending)
+            part = self.ws.get('ln.parts', (COLSUM_MAX * n1,), f32)[k * n1:(k + len(grp)) * n1]
             K.layernorm_bwd_multi([g['dcx'] for g in grp], x, [P.f(n + '.weight') for n in names], mean, rstd, dctx,
-                                  dctx, wgs, rows, D, part, defer=defer)
+                                  dctx, wgs, rows, D, part, defer=self._cs_pending)
 
     def _inputs(self, ids, pad):
         """ids [B, L] -> (int32 ids, uint8 key-padding mask or None) in the workspace."""
@@ -964,7 +830,7 @@ class VAEEngine:
                 zb = ws.get('z_bf', (B, Z))
                 K.cast_bf16(zf, zb)
                 xf, _ = self._decode(xe, zb, padm, B, L, 0.0, 0)
-                hh = self._head_hidden(xf, T)
+                hh = self._head_hidden(xf, T)[0]
                 part = ws.get('ce.part', (T, ntile, 2), f32)
                 lab_logit = ws.get('ce.label_logit', (T,), f32)
                 K.gemm(hh, P.w('input_layer.0.weight'), None, T, V, d, epi=EPI_CE_STATS,
@@ -975,71 +841,51 @@ class VAEEngine:
         return out
 
     def _head_hidden(self, xf, T):
-        """output_layer[:3] (transformer_language_model.py:55-61): LayerNorm(GELU(Linear(x))) as the bf16
-        operand of the tied vocabulary GEMM, from the decoder's bf16 output xf."""
+        """output_layer[:3] (transformer_language_model.py:55-61): hh = LayerNorm(GELU(Linear(x))) as the bf16
+        operand of the tied vocabulary GEMM, from the decoder's bf16 output xf. Returns hh and what the backward
+        needs: GELU', the LayerNorm's input h0 and its saved state."""
         d, ws, P = self.d, self.ws, self.P
         gp0 = ws.get('h0_gprime', (T, d))
         h0 = ws.get('h0', (T, d))
         K.gemm(xf, P.w('output_layer.0.weight'), h0, T, d, d, epi=EPI_GELU, bias=P.f('output_layer.0.bias'),
                aux=gp0, ldaux=d)
-        hh, _ = self._ln_fwd('output_layer.2', h0, T, 'head.ln')
-        return hh
+        hh, ln_h = self._ln_fwd('output_layer.2', h0, T, 'head.ln')
+        return hh, gp0, h0, ln_h
 
     def _decode(self, x_emb, zb, padm, B, L, dropout, seed, x_ready=False):
         """The decoder stack of reconstruct (transformer_vae.py:85-93). Returns the bf16 copy of the last layer's
         output [T, d] (the head's input; its f32 is not needed by any pass) and the layers' saved state.
-        Position 0 of every layer's input is z_projections[i](z): for layer 0 written into the embedding copy, for
-        the later layers into a [B, d] buffer the fused residual + LayerNorm pass of the layer below takes those rows
-        from (SVAE_FUSE_LN=0: the round-2 path, f32 GEMM epilogues + separate LayerNorms, for A/B runs)."""
+        Position 0 of every layer's input is z_projections[i](z): every layer's projection in one launch, spliced in
+        by the layer's first LayerNorm (the launch takes <= ZPROJ_MAX layers and a latent of <= 1024: deeper models run
+        it in chunks, wider latents a skinny GEMM per layer into the position-0 rows)."""
         hp, d, ws, P = self.hp, self.d, self.ws, self.P
         T, Z = B * L, hp.latent_depth
         if self.window and L % 32:
             raise ValueError(f'sparse decoder attention needs seq_len % 32 == 0 (SparseAttention block_size 32, '
                              f'sparse_attention.py:81), got {L}')
-        fuse = self.fuse_ln
         xs = ws.get('x_dec0', (T, d), f32)
         if not x_ready:   # (the training forward's embedding gather wrote it already)
             xs.copy_(x_emb)
         xf = ws.get('xf_bf', (T, d))
         dec = []
-        h_in = None
-        # (zf_batch: every layer's z projection in one launch, spliced in by the layer's first LayerNorm)
-        # (the launch takes <= ZPROJ_MAX layers and a latent of <= 1024: deeper models run it in chunks, wider latents
-        # the per-layer GEMM path)
-        zf_batch = self.zf_batch and not fuse and d % 8 == 0 and Z <= 1024
+        zf_batch = d % 8 == 0 and Z <= 1024
         if zf_batch:
             zall = ws.get('zproj_all', (hp.num_layers, B, d), f32)
             segs = [(P.w(f'z_projections.{i}.weight'), P.f(f'z_projections.{i}.bias'), zall[i])
                     for i in range(hp.num_layers)]
             for c0 in range(0, len(segs), ZPROJ_MAX):
                 K.zproj_fwd_multi(segs[c0:c0 + ZPROJ_MAX], zb, B, d, Z)
-        else:
-            K.gemm(zb, P.w('z_projections.0.weight'), xs, B, d, Z, ldc=L * d, epi=EPI_F32,
-                   bias=P.f('z_projections.0.bias'))
         for i in range(hp.num_layers):
             last = i + 1 == hp.num_layers
-            if fuse:
-                nxt = None
-                if not last:
-                    zrows = ws.get('zrows', (B, d), f32)
-                    K.gemm(zb, P.w(f'z_projections.{i + 1}.weight'), zrows, B, d, Z, epi=EPI_F32,
-                           bias=P.f(f'z_projections.{i + 1}.bias'))
-                    nxt = (f'decoder_layers.{i + 1}.attn_layer_norm', zrows, L, f'd{i + 1}')
-                out = None if last else ws.get(f'x_dec{i + 1}', (T, d), f32)
-            else:
-                if i > 0 and not zf_batch:
-                    K.gemm(zb, P.w(f'z_projections.{i}.weight'), xs, B, d, Z, ldc=L * d, epi=EPI_F32,
-                           bias=P.f(f'z_projections.{i}.bias'))
-                nxt, out = None, ws.get(f'x_dec{i + 1}', (T, d), f32)
+            if not zf_batch:
+                K.gemm(zb, P.w(f'z_projections.{i}.weight'), xs, B, d, Z, ldc=L * d, epi=EPI_F32,
+                       bias=P.f(f'z_projections.{i}.bias'))
+            # (the last layer's epilogue also writes the bf16 copy of its output: no separate [T, d] cast pass)
             xs, st = self.layer_fwd(f'decoder_layers.{i}.', xs, B, L, L, padm, causal=True, heads=self.H,
-                                    hd=self.hd, drop_p=dropout, seed=_mix_seed(seed, i), tag=f'd{i}', out=out,
-                                    window=self.window, fuse=fuse, h_in=h_in, next_ln=nxt,
-                                    out_bf=xf if last and (fuse or self.resid_bf16) else None,
-                                    zsplice=(zall[i], L) if zf_batch else None)
-            h_in = st.pop('next_h', None)
+                                    hd=self.hd, drop_p=dropout, seed=_mix_seed(seed, i), tag=f'd{i}',
+                                    out=ws.get(f'x_dec{i + 1}', (T, d), f32), window=self.window,
+                                    out_bf=xf if last else None, zsplice=(zall[i], L) if zf_batch else None)
             dec.append(st)
-        if not fuse and not self.resid_bf16:
-            K.cast_bf16(xs, xf)
         return xf, dec
 
     def reconstruct_f32(self, x_emb, z, pad=None):
@@ -1096,11 +942,7 @@ class VAEEngine:
         zb = ws.get('z_bf', (B, Z))
         K.cast_bf16(z, zb)
         xf, _ = self._decode(x_emb.reshape(T, d), zb, padm, B, L, 0.0, 0)
-        gp0 = ws.get('h0_gprime', (T, d))
-        h0 = ws.get('h0', (T, d))
-        K.gemm(xf, P.w('output_layer.0.weight'), h0, T, d, d, epi=EPI_GELU, bias=P.f('output_layer.0.bias'),
-               aux=gp0, ldaux=d)
-        hh, _ = self._ln_fwd('output_layer.2', h0, T, 'head.ln')
+        hh = self._head_hidden(xf, T)[0]
         logits = torch.empty(B, L, V, dtype=bf16, device=P.device)
         K.gemm(hh, P.w('input_layer.0.weight'), logits, T, V, d, epi=EPI_BF16, bias=P.f('output_layer.3.bias'))
         return logits
@@ -1115,18 +957,17 @@ class VAEEngine:
             if user_ready is not None:
                 self.flush_colsum()
                 self.flush_zproj()
-                self.join_side()
                 user_ready(end)
         if sv is None:
             raise RuntimeError('backward() without a saved forward')
         # the layers' weight-gradient GEMMs: recorded by layer_bwd, launched as one group after the encoder (flush_dw)
         self._dwq, self._dw_jobs = None, []
-        self._dw_names = self.dw_group and user_ready is None and self.side is None
+        self._dw_names = self.dw_group and user_ready is None
         B, L = sv['B'], sv['L']
         T, V, Z, N = B * L, hp.vocab_size, hp.latent_depth, hp.num_latents
         gs = ws.get('gscale', (2,), f32)
         gl = gloss.reshape(1)
-        if self.small_fused and gl.is_cuda and gl.dtype == f32:
+        if gl.is_cuda and gl.dtype == f32:
             K.step_scalars(kl_weight, gloss=gl, gs=gs)
         else:
             gs[0:1].copy_(gl)
@@ -1162,22 +1003,17 @@ class VAEEngine:
             sv['ce_q'] = q_t
         else:
             K.ce_grad(logits, V, sv['lse'], sv['chunk_w'], sv['labels'], gs[0:1], T, V, L, nch, clen)
-            # (the vocabulary-head dW stays in order: next to the equally large head dX it only contends)
-            self._dw(logits, sv['hh'], 'input_layer.0.weight', T, V, d, bias='output_layer.3.bias', on_side=False)
+            self._dw(self._job(logits, sv['hh'], 'input_layer.0.weight', T, V, d, bias='output_layer.3.bias'))
             K.gemm(logits, P.wT('input_layer.0.weight', V, d), dhh, T, d, V, epi=EPI_BF16)
         dpre0 = ws.get('b.dpre0', (T, d))
-        if self.ln_gelu:   # the head LayerNorm's backward and the GELU backward before it in one pass
-            self._ln_bwd('output_layer.2', dhh, sv['ln_h'], T, None, None, dx_bf=dpre0, gelu=sv['gp0'])
-        else:
-            dh0 = ws.get('b.dh0', (T, d), f32)
-            self._ln_bwd('output_layer.2', dhh, sv['ln_h'], T, None, dh0)
-            K.gelu_bwd(dh0, sv['gp0'], dpre0, T * d)
-        self._dw(dpre0, sv['xf'], 'output_layer.0.weight', T, d, d, bias='output_layer.0.bias')
+        # the head LayerNorm's backward and the GELU backward before it in one pass: bf16(dx * GELU')
+        self._ln_bwd('output_layer.2', dhh, sv['ln_h'], T, None, None, dx_bf=dpre0, gelu=sv['gp0'])
+        self._dw(self._job(dpre0, sv['xf'], 'output_layer.0.weight', T, d, d, bias='output_layer.0.bias'))
         dx = ws.get('b.dx_dec', (T, d), f32)
         # (the same epilogue writes the top decoder layer's dropout-masked bf16 FFN-output gradient, b.g2: no
-        # separate dropout_bwd_cast pass over [T, d]; SVAE_HEAD_G2=0 for A/B runs)
+        # separate dropout_bwd_cast pass over [T, d])
         top = sv['dec_layers'][-1]
-        g2_pre = self.head_g2 and top['rows_q'] == T
+        g2_pre = top['rows_q'] == T
         K.gemm(dpre0, P.wT('output_layer.0.weight', d, d), dx, T, d, d, epi=EPI_F32,
                aux=ws.get(self._bname('b.g2', top), (T, d)) if g2_pre else None, ldaux=d if g2_pre else 0,
                drop_p=top['drop_p'] if g2_pre else 0.0, seed=top['seed'] if g2_pre else 0)
@@ -1199,26 +1035,24 @@ class VAEEngine:
                 nd = (nst['drop_p'], nst['seed'], L)
             # position-0 splice: its gradient feeds z_projections[i]; earlier layers see zero there (moved out of dx by
             # the layer's last LayerNorm backward when it is a residual layer)
-            dzh_i = ws.get('b.dzh_all', (hp.num_layers, B, d), f32)[i] if self.zp_batch else dzh
+            dzh_i = ws.get('b.dzh_all', (hp.num_layers, B, d), f32)[i]
             zs = (L, dzh_i, None) if st['resid'] and st['rows_q'] == T else None
             self.layer_bwd(st, dx, dx_prev, g2_ready=g2_ready, next_drop=nd, zsplice=zs,
                            next_st=sv['dec_layers'][i - 1] if nd is not None else None)
             g2_ready = nd is not None
             wz, bz = f'z_projections.{i}.weight', f'z_projections.{i}.bias'
-            if zs is not None and self.zp_batch:
+            if zs is not None:
                 # dW, d bias and dz of z_projections[i]: deferred, then every layer's in one launch (flush_zproj, also
                 # at each data-parallel bucket point); dz sums the layers in this loop's order either way
                 if len(self._zp_pending) == ZPROJ_MAX:
                     self.flush_zproj()
                 self._zp_ctx = (sv['z_bf'], dz, B, d, Z)
                 self._zp_pending.append((dzh_i, P.w(wz), P.g(wz), P.g(bz)))
-            elif zs is not None:   # dW, d bias and dz of z_projections[i] in one f32 launch
-                K.zproj_bwd(dzh, sv['z_bf'], P.w(wz), P.g(wz), P.g(bz), dz, B, d, Z)
             else:
                 self.flush_zproj()
                 K.extract_rows(dx_prev, d, T, L, d, dzh)
                 K.cast_bf16(dzh, dzh_bf)
-                self._dw(dzh_bf, sv['z_bf'], wz, B, d, Z, bias=bz)   # (bias gradient = the fused row sums)
+                self._dw(self._job(dzh_bf, sv['z_bf'], wz, B, d, Z, bias=bz))   # (bias gradient = the fused row sums)
                 # dz += dzh . W_i: a 64 x 64 output over K = d -> split K over blocks (f32 atomics into dz)
                 K.gemm(dzh_bf, P.w(wz), dz, B, Z, d, b_t=True, epi=EPI_F32_ATOMIC, splits=max(1, min(8, d // 64)))
             ready(P.end(f'z_projections.{i}.bias'))
@@ -1231,7 +1065,7 @@ class VAEEngine:
         K.reparam_bwd(sv['stats'], sv['eps'], dz, sv['ntok'], gs[1:2], dstats, B, Z)
         dstats_bf = ws.get('b.dstats_bf', (B, 2 * Z))
         K.cast_bf16(dstats, dstats_bf)
-        self._dw(dstats_bf, sv['enc_bf'], 'q_of_z_given_x.linear.weight', B, 2 * Z, d)
+        self._dw(self._job(dstats_bf, sv['enc_bf'], 'q_of_z_given_x.linear.weight', B, 2 * Z, d))
         self._db(dstats, 'q_of_z_given_x.linear.bias', B, 2 * Z)
         denc = ws.get('b.denc', (B, d), f32)
         K.gemm(dstats_bf, P.w('q_of_z_given_x.linear.weight'), denc, B, d, 2 * Z, b_t=True, epi=EPI_F32)
@@ -1255,7 +1089,6 @@ class VAEEngine:
             tmp = ws.get('b.dfirst', (T, d), f32)
             self.layer_bwd(st0, dcur, tmp)
             self.flush_dw()
-            self.join_side()        # the tied weight's head gradient (side stream) before the scatter-add
             K.embedding_bwd(sv['ids32'], tmp, P.g('input_layer.0.weight'), T, d)   # (the head's part: below)
         else:
             self.layer_bwd(st0, dcur, dx_emb, dx_accumulate=True)
@@ -1263,11 +1096,9 @@ class VAEEngine:
 
         ready(P.end('encoder.first_layer.ffn_layer_norm.bias'))
         # ---- embedding (tied with the head weight)
-        self.join_side()            # the tied weight's head gradient (side stream) before the scatter-add
         self._embedding_bwd(sv, dx_emb, T, d)
         ready(P.n_live)
         self.flush_colsum()
-        self.join_side()
 
     def _embedding_bwd(self, sv, dx, T, d):
         """Scatter-add of d x_emb into the tied table; with the P-head, fused with the head's one-hot dW part."""

@@ -3,6 +3,7 @@ arguments it relies on and raises on a non-zero status. All work is enqueued on 
 stream; nothing here synchronises."""
 import ctypes
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -106,6 +107,20 @@ def auto_splits(M, N_, K, target=512):
     return max(1, s)
 
 
+class DwJob(NamedTuple):
+    """One weight-gradient GEMM, linear_dw's arguments: what linear_dw_pair and linear_dw_group take (a plain tuple
+    of all nine in this order also does)."""
+    dY: torch.Tensor
+    X: torch.Tensor
+    Wgrad: torch.Tensor
+    rows: int
+    n_out: int
+    n_in: int
+    ldy: int = None
+    ldx: int = None
+    bgrad: torch.Tensor = None
+
+
 def linear_dw(dY, X, Wgrad, rows, n_out, n_in, ldy=None, ldx=None, bgrad=None):
     """Wgrad[n_out, n_in] += dY^T . X over `rows` rows (dY [rows, n_out] bf16, X [rows, n_in] bf16); with
     bgrad, also bgrad[n_out] += column sums of dY (the bias gradient, fused into the same pass over dY)."""
@@ -150,22 +165,22 @@ def pair_splits(shapes):
 
 
 def linear_dw_pair(j0, j1):
-    """Two linear_dw's (each (dY, X, Wgrad, rows, n_out, n_in, ldy, ldx, bgrad)) as one paired launch: each needs
-    only ~half the split-K slices it would take alone to fill the chip (half the slab bytes written and reduced).
-    Falls back to two linear_dw calls for shapes that would not split."""
-    sp = pair_splits([(j[4], j[5], j[3]) for j in (j0, j1)])
+    """Two linear_dw's (DwJobs) as one paired launch: each needs only ~half the split-K slices it would take alone
+    to fill the chip (half the slab bytes written and reduced). Falls back to two linear_dw calls for shapes that
+    would not split."""
+    j0, j1 = DwJob._make(j0), DwJob._make(j1)
+    sp = pair_splits([(j.n_out, j.n_in, j.rows) for j in (j0, j1)])
     if sp is None:
-        linear_dw(*j0[:8], bgrad=j0[8])
-        linear_dw(*j1[:8], bgrad=j1[8])
+        linear_dw(*j0)
+        linear_dw(*j1)
         return
-    n0, n1 = sp[0] * j0[4] * j0[5], sp[1] * j1[4] * j1[5]
-    slab = _slab_workspace(n0 + n1, j0[0].device)
+    n0, n1 = sp[0] * j0.n_out * j0.n_in, sp[1] * j1.n_out * j1.n_in
+    slab = _slab_workspace(n0 + n1, j0.dY.device)
     gs = []
     for j, aux, s in ((j0, slab[:n0], sp[0]), (j1, slab[n0:n0 + n1], sp[1])):
-        dY, X, Wg, rows, n_out, n_in, ldy, ldx, bg = j
-        gs.append(((dY, X, Wg, n_out, n_in, rows),
-                   dict(a_t=True, b_t=True, lda=ldy or n_out, ldb=ldx or n_in, ldc=n_in, epi=N.EPI_F32_ATOMIC,
-                        splits=s, a_rowsum=bg, aux=aux)))
+        gs.append(((j.dY, j.X, j.Wgrad, j.n_out, j.n_in, j.rows),
+                   dict(a_t=True, b_t=True, lda=j.ldy or j.n_out, ldb=j.ldx or j.n_in, ldc=j.n_in,
+                        epi=N.EPI_F32_ATOMIC, splits=s, a_rowsum=j.bgrad, aux=aux)))
     gemm_pair(*gs)
 
 
@@ -238,30 +253,31 @@ class DwGroupState:
 
 
 def linear_dw_group(jobs, splits, state, slab=None, max_blocks=0):
-    """linear_dw for every job ((dY, X, Wgrad, rows, n_out, n_in, ldy, ldx, bgrad) each) in one grouped pass
+    """linear_dw for every job (DwJobs) in one grouped pass
     (svae_gemm_group): the jobs with slab[i] false (default: splits[i] == 1) accumulate whole-K tiles straight into
     Wgrad in one launch; the others store splits[i] K slices into slabs in a second launch, added into Wgrad in slice
     order by one reduction launch. max_blocks > 0 caps the blocks per launch (they then walk several tiles each)."""
+    jobs = [DwJob._make(j) for j in jobs]
     n = len(jobs)
     if n == 0:
         return
     if n > N.GROUP_MAX:
         raise RuntimeError(f'linear_dw_group: {n} GEMMs (at most {N.GROUP_MAX})')
     slab = [s > 1 for s in splits] if slab is None else slab
-    need = sum(s * j[4] * j[5] for j, s, sb in zip(jobs, splits, slab) if sb)
-    ws = _slab_workspace(need, jobs[0][0].device) if need else None
+    need = sum(s * j.n_out * j.n_in for j, s, sb in zip(jobs, splits, slab) if sb)
+    ws = _slab_workspace(need, jobs[0].dY.device) if need else None
     state.ensure(n)
     off = 0
     for i, (j, s, sb) in enumerate(zip(jobs, splits, slab)):
-        dY, X, Wg, rows, n_out, n_in, ldy, ldx, bg = j
         aux = None
         if sb:
-            aux = ws[off:off + s * n_out * n_in]
-            off += s * n_out * n_in
+            aux = ws[off:off + s * j.n_out * j.n_in]
+            off += s * j.n_out * j.n_in
         elif s != 1:
             raise RuntimeError('linear_dw_group: a GEMM without a slab has one split')
-        _fill_desc(state.descs[i], dY, X, Wg, n_out, n_in, rows, a_t=True, b_t=True, lda=ldy or n_out, ldb=ldx or n_in,
-                   ldc=n_in, epi=N.EPI_F32_ATOMIC if sb else N.EPI_F32_ACC, splits=s, a_rowsum=bg, aux=aux)
+        _fill_desc(state.descs[i], j.dY, j.X, j.Wgrad, j.n_out, j.n_in, j.rows, a_t=True, b_t=True,
+                   lda=j.ldy or j.n_out, ldb=j.ldx or j.n_in, ldc=j.n_in,
+                   epi=N.EPI_F32_ATOMIC if sb else N.EPI_F32_ACC, splits=s, a_rowsum=j.bgrad, aux=aux)
     check(lib.svae_gemm_group(state.descs, n, max_blocks, state.table.data_ptr(), state.host, state.bytes, stream()),
           'svae_gemm_group')
 

@@ -38,6 +38,50 @@ def test_library_exports_every_header_symbol():
     assert set(names) == set(_native.EXPORTED)
 
 
+def header_prototypes():
+    """{name: (return type, [parameter type, ...])} of every function the header declares, as C type strings
+    without the parameter names."""
+    src = open(HEADER).read()
+    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r'^\s*(int|int32_t|int64_t|const char\*)\s+(svae_\w+)\s*\(([^)]*)\)\s*;', src,
+                                        flags=re.M):
+        params = ' '.join(params.split())
+        types = []
+        for p in ([] if params in ('', 'void') else params.split(',')):
+            t = re.sub(r'\w+$', '', p.strip())          # drop the parameter's name
+            types.append(re.sub(r'\s*\*\s*', '*', t).strip())
+        protos[name] = (ret, types)
+    return protos
+
+
+def ctype_of(t):
+    """The ctypes type _native declares for a parameter of C type t."""
+    import ctypes
+    from sparse_vae import _native
+    bare = re.sub(r'\bconst\b', '', t).replace(' ', '')
+    if bare in ('svae_gemm_desc*', 'svae_attn_desc*'):
+        return ctypes.POINTER(_native.GemmDesc if 'gemm' in bare else _native.AttnDesc)
+    if bare.endswith('*') or bare == 'svae_stream_t':
+        return ctypes.c_void_p
+    return {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint64_t': ctypes.c_uint64,
+            'float': ctypes.c_float}[bare]
+
+
+def test_ctypes_signatures_match_header():
+    """Every function's argtypes (type by type, in order) and restype are what the header's prototype says: a wrong
+    width or a swapped argument in _native._SIGS fails here, not on the device."""
+    import ctypes
+    from sparse_vae import _native
+    protos = header_prototypes()
+    assert set(protos) == set(header_functions())
+    rets = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'const char*': ctypes.c_char_p}
+    for name, (ret, types) in sorted(protos.items()):
+        fn = getattr(_native.lib, name)
+        assert list(fn.argtypes) == [ctype_of(t) for t in types], (name, types)
+        assert fn.restype is rets[ret], (name, ret)
+
+
 def test_version_string():
     from sparse_vae import _native
     assert _native.lib.svae_version().startswith(b'libsvae')
