@@ -52,7 +52,8 @@ enum svae_epi {
                                  labels[m] != 0, else 0 (exponent clamped at 2^127); aux f32
                                  [ceil(N/128)][M] (tile-major) = per (128-col tile, row) sums of them  */
   SVAE_EPI_ROWSCALE_GATHER = 10 /* C bf16 = alpha * row_a[m] * acc - row_b[m] * gather[labels[m]][n]
-                                 (the gather term is skipped where labels[m] == 0)                    */
+                                 (the gather term is skipped where labels[m] == 0); N % 8 == 0 (the
+                                 gather row is read 8 columns at a time), else SVAE_EINVAL            */
 };
 
 typedef struct svae_gemm_desc {
@@ -321,9 +322,10 @@ int svae_ce_grad(void* logits, int64_t ld, const float* lse, const float* chunk_
  * finds every labelled row whose sum of P reaches 2^100 (or is not finite), lists it in sat_ws (int32 [1 + rows]:
  * count, then rows; the count stays readable after the call) and recomputes it exactly: the row's logits from hh, W
  * and bias, P[row] = exp(logit - max) (bf16, into P with leading dimension ldp), lse = max + log sum, row_loss =
- * lse - c, and row_off[row] = max -- so the backward (which reads P, row_off and lse) stays consistent. At most 1024
- * rows are recomputed (~5 ms worst case at V = 32768, D = 512); past that the step is diverging, the remaining rows
- * keep their overflowed P (their loss is infinite) and the count still lists every flagged row.
+ * lse - c, and row_off[row] = max -- so the backward (which reads P, row_off and lse) stays consistent. Every flagged
+ * row is recomputed, however many there are (64 blocks stride over the list, ~0.3 ms per round at V = 32768, D = 512):
+ * an overflowed P left in place would feed inf / NaN gradients to the clip and the optimiser, where the reference's
+ * log-softmax stays finite.
  * ce_prob_finalize = ce_prob_finalize_fix without the check (sat_ws = NULL). */
 int svae_ce_label_logit(const void* hh, int64_t ldh, const void* W, int64_t ldw, const float* bias,
                         const int32_t* labels, int32_t rows, int32_t D, float* out, svae_stream_t stream);

@@ -1735,7 +1735,10 @@ static int validate_desc(const svae_gemm_desc* d) {
   // the P-head epilogues (CE_PROB, ROWSCALE_GATHER) and weighted row sums exist in the 256x256 kernel only
   if (epi_new && (d->a_t || d->splits != 1 || d->batch != 1 || !d->labels || !d->row_a)) return SVAE_EINVAL;
   if (d->epi == SVAE_EPI_CE_PROB && !d->aux) return SVAE_EINVAL;
-  if (d->epi == SVAE_EPI_ROWSCALE_GATHER && (!d->row_b || !d->gather || d->ldg % 8 || ((uintptr_t)d->gather & 15)))
+  // (N % 8: the epilogue loads the gather row in 16-B pieces of 8 columns; a 4-column tail would be stored without
+  // its gather term)
+  if (d->epi == SVAE_EPI_ROWSCALE_GATHER &&
+      (!d->row_b || !d->gather || d->ldg % 8 || ((uintptr_t)d->gather & 15) || d->N % 8))
     return SVAE_EINVAL;
   // k-weighted row sums: one split (F32_ACC), or split-K slab mode (F32_ATOMIC with aux)
   if (d->k_weight && (!d->a_rowsum || !d->a_t || (d->splits != 1 && !(d->epi == SVAE_EPI_F32_ATOMIC && d->aux))))
