@@ -552,6 +552,46 @@ int svae_latent_topk(int32_t metric, const float* q_mu, const float* q_scale, co
                      const float* inv_norm, int32_t N, int32_t Z, int32_t k, void* ws, int64_t ws_bytes, float* scores,
                      int32_t* indices, svae_stream_t stream);
 
+/* ---- t-SNE of the latent index: exact, two output dimensions (tsne.py:16-30, where the embedding is tsnecuda's or
+ * sklearn's) --------------------------------------------------------------------------------------------
+ * The k-NN graph is dist f32 [N][k], nbr int32 [N][k] (LatentIndex.knn_graph); 1 <= k <= 64, N * k < 2^31. y, rep,
+ * attr, vel, gains are f32 [N][2], 8-byte aligned; N >= 2 (tsne_affinities, a per-row operation, takes N >= 1);
+ * tsne_repulse, its two companions (which return 0) and tsne_update also reject N > 2^24.
+ * Nothing below uses an atomic: every sum has a fixed order and two calls on one input agree bit for bit.
+ * tsne_affinities: per row the conditional p_j = exp(-beta (d_j - d_min)) / sum, beta found by bisection (start 1,
+ *   doubled / halved while one bracket is open, at most 100 steps) until the entropy is within 1e-5 of
+ *   log(perplexity); 1 < perplexity < k. p f32 [N][k] (each row sums to 1), beta f32 [N]. Precise expf / logf; the
+ *   exponent carries the rounding errors of d_j - d_min and of the product, so a p is accurate relative to itself.
+ *   Rows of equal distances come out uniform; rows with more tied minima than the perplexity share 1 among the ties.
+ * tsne_repulse: with q_ij = 1 / (1 + |y_i - y_j|^2): rep_i = sum_{j != i} q_ij^2 (y_i - y_j), zrow_i =
+ *   sum_{j != i} q_ij, zsum = sum_i zrow_i. j = i is excluded by index (duplicate points are legal: q = 1, no
+ *   force). Three launches: a (row block, column slice) grid of workgroups, each over SVAE_TSNE_ROWS_PER_BLOCK rows
+ *   (two per lane) and the slice's columns in LDS tiles of SVAE_TSNE_TILE_COLS, leaves per-slice partials in ws; one
+ *   thread per row adds the slices in order; one workgroup adds the rows' zrow (in f64). A slice is
+ *   svae_tsne_repulse_slice_cols(N) columns (a multiple of the tile), chosen from N alone so that the grid reaches
+ *   about 2048 workgroups where N allows. ws: caller-owned, 8-byte aligned, >= svae_tsne_repulse_ws_bytes(N) =
+ *   slices * 3 * N * 4 (rounded up to 8) + ceil(N / 256) * 8 bytes; its contents need not survive.
+ * tsne_attract: attr_i = sum over row i's own edges (j = nbr[i][s]) of p[i][s] q_ij (y_i - y_j) + sum over the edges
+ *   that point at i (e = j * k + s with nbr[j][s] = i) of p[j][s] q_ij (y_i - y_j): the two directed halves of the
+ *   symmetrised affinity (p_{j|i} + p_{i|j}) / 2N, whose 1 / 2N the update applies. rev_ptr int32 [N + 1] and rev_edge
+ *   int32 [N * k] are the edge ids grouped by target (sparse_vae.tsne.reverse_edges). One wave per row; neighbour
+ *   and edge ids are clamped into range before they index anything.
+ * tsne_update: in place, per coordinate: g = 4 (exaggeration / (2 N) * attr - rep / zsum); gains += 0.2 where vel and g
+ *   have strictly opposite signs, else gains *= 0.8, floor 0.01; vel = momentum * vel - learning_rate * gains * g;
+ *   y += vel. zsum is read from the device. */
+#define SVAE_TSNE_ROWS_PER_BLOCK 512
+#define SVAE_TSNE_TILE_COLS 256
+int svae_tsne_affinities(const float* dist, int32_t N, int32_t k, float perplexity, float* p, float* beta,
+                         svae_stream_t stream);
+int64_t svae_tsne_repulse_slice_cols(int32_t N);
+int64_t svae_tsne_repulse_ws_bytes(int32_t N);
+int svae_tsne_repulse(const float* y, int32_t N, void* ws, int64_t ws_bytes, float* rep, float* zrow, float* zsum,
+                      svae_stream_t stream);
+int svae_tsne_attract(const float* y, const int32_t* nbr, const float* p, const int32_t* rev_ptr,
+                      const int32_t* rev_edge, int32_t N, int32_t k, float* attr, svae_stream_t stream);
+int svae_tsne_update(float* y, float* vel, float* gains, const float* attr, const float* rep, const float* zsum,
+                     int32_t N, float exaggeration, float learning_rate, float momentum, svae_stream_t stream);
+
 /* library identification: returns a static string (build id, target arch). */
 const char* svae_version(void);
 

@@ -22,6 +22,7 @@ EPI_BF16, EPI_F32, EPI_F32_ACC, EPI_F32_ATOMIC, EPI_GELU, EPI_GELU_BWD, EPI_DROP
 LATENT_L2, LATENT_COSINE, LATENT_KL = range(3)      # enum svae_latent_metric
 LATENT_METRICS = {'l2': LATENT_L2, 'cosine': LATENT_COSINE, 'kl': LATENT_KL}
 LATENT_MAX_BLOCKS = 1024                             # SVAE_LATENT_MAX_BLOCKS
+TSNE_ROWS_PER_BLOCK, TSNE_TILE_COLS = 512, 256       # SVAE_TSNE_ROWS_PER_BLOCK, SVAE_TSNE_TILE_COLS
 
 
 class GemmDesc(ctypes.Structure):
@@ -195,6 +196,13 @@ _SIGS = {
     'svae_latent_topk_ws_bytes': [c_int32, c_int32],
     'svae_latent_topk': [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                          c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+    'svae_tsne_affinities': [c_void_p, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p],
+    'svae_tsne_repulse_slice_cols': [c_int32],
+    'svae_tsne_repulse_ws_bytes': [c_int32],
+    'svae_tsne_repulse': [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
+    'svae_tsne_attract': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
+    'svae_tsne_update': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_float,
+                         c_float, c_void_p],
     'svae_version': [],
 }
 
@@ -210,6 +218,7 @@ def _load():
         fn.restype = {'svae_version': ctypes.c_char_p, 'svae_attn_dq_part_elems': c_int64,
                       'svae_attn_dq_part_elems_w': c_int64, 'svae_attn_fwd_ws_elems': c_int64,
                       'svae_latent_topk_ws_bytes': c_int64,
+                      'svae_tsne_repulse_slice_cols': c_int64, 'svae_tsne_repulse_ws_bytes': c_int64,
                       'svae_gemm_group_table_bytes': c_int64}.get(name, ctypes.c_int)
     return lib
 

@@ -924,3 +924,93 @@ def latent_topk(metric, query, corpus, k):
     check(lib.svae_latent_topk(metric, *args_q, *args_c, k, ws.data_ptr(), nbytes, scores.data_ptr(),
                                indices.data_ptr(), stream()), 'svae_latent_topk')
     return scores, indices
+
+
+def _tsne_f32(t, *shape):
+    _dev(t)
+    assert t.dtype == f32 and t.is_contiguous() and tuple(t.shape) == shape, (tuple(t.shape), shape)
+    return t
+
+
+def _tsne_graph_shape(n, k):
+    if n * k >= 2 ** 31:
+        raise ValueError(f'tsne: N * k = {n * k} does not fit the int32 edge ids')
+    if not 1 <= k <= 64:
+        raise ValueError(f'tsne: k = {k} outside 1..64')
+
+
+def tsne_affinities(dist, perplexity):
+    """svae_tsne_affinities: dist f32 [N, k] (a row's neighbour dissimilarities) -> (p f32 [N, k], beta f32 [N]): per
+    row the Gaussian conditional whose entropy is log(perplexity), and the precision found for it."""
+    _dev(dist)
+    assert dist.dtype == f32 and dist.dim() == 2 and dist.is_contiguous()
+    n, k = dist.shape
+    _tsne_graph_shape(n, k)
+    if not 1.0 < perplexity < k:
+        raise ValueError(f'tsne_affinities: perplexity {perplexity} outside (1, k = {k})')
+    p = torch.empty_like(dist)
+    beta = torch.empty(n, dtype=f32, device=dist.device)
+    if n:
+        check(lib.svae_tsne_affinities(dist.data_ptr(), n, k, float(perplexity), p.data_ptr(), beta.data_ptr(),
+                                       stream()), 'svae_tsne_affinities')
+    return p, beta
+
+
+def tsne_repulse_geometry(n):
+    """(rows per workgroup, column slices, columns per slice) of svae_tsne_repulse at n rows."""
+    cols = lib.svae_tsne_repulse_slice_cols(n)
+    return N.TSNE_ROWS_PER_BLOCK, -(-n // cols), cols
+
+
+def tsne_repulse(y, rep=None, zrow=None, zsum=None):
+    """svae_tsne_repulse: y f32 [N, 2] -> (rep f32 [N, 2], zrow f32 [N], zsum f32 [1]), the exact all-pairs Student-t
+    repulsion and its normaliser. The slice workspace is allocated per call (stream-ordered by the caching
+    allocator)."""
+    n = y.shape[0]
+    _tsne_f32(y, n, 2)
+    if n < 2:
+        raise ValueError('tsne_repulse: at least two points')
+    dev = y.device
+    rep = torch.empty_like(y) if rep is None else _tsne_f32(rep, n, 2)
+    zrow = torch.empty(n, dtype=f32, device=dev) if zrow is None else _tsne_f32(zrow, n)
+    zsum = torch.empty(1, dtype=f32, device=dev) if zsum is None else _tsne_f32(zsum, 1)
+    nbytes = lib.svae_tsne_repulse_ws_bytes(n)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    check(lib.svae_tsne_repulse(y.data_ptr(), n, ws.data_ptr(), nbytes, rep.data_ptr(), zrow.data_ptr(),
+                                zsum.data_ptr(), stream()), 'svae_tsne_repulse')
+    return rep, zrow, zsum
+
+
+def tsne_attract(y, nbr, p, rev_ptr, rev_edge, attr=None):
+    """svae_tsne_attract: the attraction over the k-NN edges in both directions. nbr int32 [N, k], p f32 [N, k] (the
+    conditional affinities), rev_ptr int32 [N + 1] / rev_edge int32 [N * k] from sparse_vae.tsne.reverse_edges ->
+    attr f32 [N, 2] (without the 1 / 2N of the symmetrisation: tsne_update applies it)."""
+    n = y.shape[0]
+    _tsne_f32(y, n, 2)
+    _dev(nbr, rev_ptr, rev_edge)
+    assert nbr.dim() == 2 and nbr.shape[0] == n
+    k = nbr.shape[1]
+    if n < 2:
+        raise ValueError('tsne_attract: at least two points')
+    _tsne_graph_shape(n, k)
+    _tsne_f32(p, n, k)
+    for t, m in ((nbr, n * k), (rev_ptr, n + 1), (rev_edge, n * k)):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == m
+    attr = torch.empty_like(y) if attr is None else _tsne_f32(attr, n, 2)
+    check(lib.svae_tsne_attract(y.data_ptr(), nbr.data_ptr(), p.data_ptr(), rev_ptr.data_ptr(), rev_edge.data_ptr(),
+                                n, k, attr.data_ptr(), stream()), 'svae_tsne_attract')
+    return attr
+
+
+def tsne_update(y, vel, gains, attr, rep, zsum, exaggeration, learning_rate, momentum):
+    """svae_tsne_update, in place on y, vel, gains (f32 [N, 2]): one step of van der Maaten's optimiser from the
+    attraction, the repulsion and its normaliser zsum (f32 [1], read on the device)."""
+    n = y.shape[0]
+    if n < 2:
+        raise ValueError('tsne_update: at least two points')
+    for t in (y, vel, gains, attr, rep):
+        _tsne_f32(t, n, 2)
+    _tsne_f32(zsum, 1)
+    check(lib.svae_tsne_update(y.data_ptr(), vel.data_ptr(), gains.data_ptr(), attr.data_ptr(), rep.data_ptr(),
+                               zsum.data_ptr(), n, float(exaggeration), float(learning_rate), float(momentum),
+                               stream()), 'svae_tsne_update')

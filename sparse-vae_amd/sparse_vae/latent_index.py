@@ -161,6 +161,36 @@ class LatentIndex:
         scores, indices = K.latent_topk(metric, self._query(query), corpus, int(k))
         return scores, indices.to(torch.int64)
 
+    def knn_graph(self, k: int, metric: str = 'l2', chunk: int = 512):
+        """Every row's k nearest other rows, best first: (dist f32 [N, k], idx int32 [N, k]) on the device, the graph
+        t-SNE starts from. metric: 'l2' or 'kl' (dissimilarities). Built on `search`: the rows go through
+        svae_latent_topk in chunks of `chunk` queries with k + 1 hits each, and the row itself is taken out by index
+        (duplicates tie and ties go to the lower row, so a row is not always its own first hit; where it is not among
+        its k + 1 hits the last one is dropped). No score is recomputed: a distance is bit-identical to `search`'s.
+        Nothing in the loop synchronises with the host."""
+        if metric not in ('l2', 'kl'):
+            raise ValueError(f"knn_graph: metric must be 'l2' or 'kl' (a dissimilarity), got '{metric}'")
+        corpus = self._corpus()
+        n, k, chunk = self._n, int(k), int(chunk)
+        if not 1 <= k <= min(63, n - 1):
+            raise ValueError(f'knn_graph: k = {k} outside 1..min(63, {n} rows - 1)')
+        if chunk < 1:
+            raise ValueError('knn_graph: chunk must be positive')
+        dev = self._device
+        dist = torch.empty(n, k, dtype=torch.float32, device=dev)
+        idx = torch.empty(n, k, dtype=torch.int32, device=dev)
+        rows = torch.arange(n, dtype=torch.int32, device=dev)
+        for c0 in range(0, n, chunk):
+            c1 = min(n, c0 + chunk)
+            query = (self._loc[c0:c1], self._scale[c0:c1], self._logdet[c0:c1], self._inv_norm[c0:c1])
+            s, i = K.latent_topk(metric, query, corpus, k + 1)
+            drop = i == rows[c0:c1, None]
+            drop[:, -1] |= ~drop.any(dim=1)
+            keep = torch.argsort(drop.to(torch.int8), dim=1, stable=True)[:, :k]   # the k kept hits, in their order
+            dist[c0:c1] = s.gather(1, keep)
+            idx[c0:c1] = i.gather(1, keep)
+        return dist, idx
+
     def scores(self, query, metric: str = 'l2'):
         """The dense [Q, N] score matrix of `metric` (svae_latent_scores)."""
         if metric not in METRICS:
