@@ -201,7 +201,10 @@ int svae_colsum_multi(const svae_colsum_seg* segs, int32_t n, svae_stream_t stre
  * q/k/v/o: bf16 rows of H*hd (token-major, head-interleaved, exactly the nn.Linear output layout),
  * row strides sq/sk/sv/so elements, batch strides bq/bk/bv/bo elements (bq = 0 for learned queries).
  * key_pad: uint8 [B][Lk] (1 = masked, padded_tensor.py:16) or NULL. causal: mask key > query
- * (attention.py:85-95). lse: f32 [B][H][Lq]. scale = hd^-0.5 (attention.py:83). */
+ * (attention.py:85-95). lse: f32 [B][H][Lq]. scale = hd^-0.5 (attention.py:83). hd: any multiple of 8 up to 128 (the
+ * kernels are built for 64, 96 and 128 dims; another size runs the next one up with its loads and stores cut at hd).
+ * A query with no visible key (every key of its batch entry padded) gets O = 0 and lse = -inf, and the backward
+ * gives it and its entry's keys zero gradients. */
 typedef struct svae_attn_desc {
   const void* q; const void* k; const void* v; void* o;
   int64_t sq, sk, sv, so, bq, bk, bv, bo;

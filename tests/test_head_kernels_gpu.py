@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import head_ref as R
+from sentinels import SENTINEL, dev, flat, g, intact, matrix, ratio, report
 
 pytestmark = pytest.mark.gpu
 
@@ -19,47 +20,7 @@ if torch.cuda.is_available():
     from sparse_vae import kernels as K
     from sparse_vae import _native as N
 
-dev = 'cuda'
-GUARD = 64
-XROWS = 3                         # sentinel rows below a matrix output
-SENTINEL = -7777.0
 f32, bf16, i32 = torch.float32, torch.bfloat16, torch.int32
-
-
-def g(t):
-    return t.to(dev)
-
-
-def flat(n, dtype=f32, fill=SENTINEL):
-    """-> (buffer, view of its first n elements); the GUARD elements after them hold the sentinel."""
-    full = torch.full((n + GUARD,), SENTINEL, dtype=dtype, device=dev)
-    full[:n] = fill
-    return full, full[:n]
-
-
-def matrix(rows, cols, ld, dtype, fill=SENTINEL):
-    """-> (buffer [rows + XROWS, ld], view [rows, cols]); everything outside the view holds the sentinel."""
-    full = torch.full((rows + XROWS, ld), SENTINEL, dtype=dtype, device=dev)
-    full[:rows, :cols] = fill
-    return full, full[:rows, :cols]
-
-
-def intact(full, rows=None, cols=None):
-    """The sentinels of flat() / matrix() survived."""
-    s = torch.tensor(SENTINEL, dtype=full.dtype)
-    if full.dim() == 1:
-        return bool((full[-GUARD:] == s).all().item())
-    return bool((full[rows:] == s).all().item() and (full[:, cols:] == s).all().item())
-
-
-def report(what, got, limit):
-    print(f'{what}: {got:.3e} (bound {limit:.3e})')
-    assert got <= limit, (what, got, limit)
-
-
-def ratio(what, got):
-    print(f'{what}: {got:.3f} of its allowance')
-    assert got <= 1.0, (what, got)
 
 
 SHAPES = pytest.mark.parametrize('T,V,D', R.KERNEL_SHAPES)
