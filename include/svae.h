@@ -595,6 +595,51 @@ int svae_tsne_attract(const float* y, const int32_t* nbr, const float* p, const 
 int svae_tsne_update(float* y, float* vel, float* gains, const float* attr, const float* rep, const float* zsum,
                      int32_t N, float exaggeration, float learning_rate, float momentum, svae_stream_t stream);
 
+/* ---- aggregate-posterior diagnostics: the sums behind the MMD estimators of math_utils.py:104-184, and the
+ * per-dimension statistics of the latent index (csrc/mmd.hip) ---------------------------------------------------
+ * Rows are f32 [rows][Z], 16-byte aligned, Z a multiple of 4 in 4..256; 1 <= rows <= 2^24. Every f64 result leaves
+ * through a device pointer. Nothing below uses an atomic: grids and summation orders depend on the shapes alone, so
+ * two calls on one input agree bit for bit. ws: caller-owned, 8-byte aligned, contents need not survive.
+ * svae_pairsum: out[p] (f64 [P] on the device, 1 <= P <= 8) = sum over the pairs of k_p(d2(x_i, y_j) + c_j), with
+ *   d2 the squared distance formed from direct differences (fmaf of (x - y)^2, so its error is relative to d2 itself
+ *   whatever offset the rows share). triangular != 0: y is ignored (may be NULL or x), M must equal N, the pairs are
+ *   i < j (what pdist enumerates), N >= 2, col_off must be NULL. triangular == 0: all N * M pairs of x [N][Z] with
+ *   y [M][Z]; col_off f32 [M] or NULL (= 0) is added to d2 before the kernel function (the IMQ cross term of
+ *   math_utils.py:181 is not a true distance). kind SVAE_PAIR_RBF: k_p = exp(-params[p] * d2), params[p] >= 0;
+ *   SVAE_PAIR_IMQ: k_p = params[p] / (params[p] + d2), params[p] > 0. params is a HOST pointer to P floats, read
+ *   during the call. A workgroup owns svae_pairsum_geometry's rows (a lane holds its rows in registers) against a
+ *   slice of the columns in LDS tiles of SVAE_PAIRSUM_TILE_COLS; a term is added in f32 only within one tile (at most
+ *   SVAE_PAIRSUM_TILE_COLS terms per accumulator), from there on in f64. ws >= svae_pairsum_ws_bytes(...) =
+ *   row_blocks * slices * 8 * 8 bytes.
+ * svae_pairsum_geometry: geom (HOST int32 [5]) = {rows per workgroup (512 for Z <= 64, else 256), row blocks, column
+ *   slices, columns per slice (a multiple of the tile), tile columns}; returns 1 (nothing written) on a bad shape.
+ * svae_mmd_rowterm: out (f64 [1]) = sum_i exp(-0.5 sum_j (x_ij - m_j)^2 w_j); m f32 [Z] or NULL (= 0), w f32 [Z].
+ *   ws >= svae_mmd_rowterm_ws_bytes(N).
+ * svae_latent_colstats: per latent dimension over the N rows of loc / scale, in f64: mean_loc, var_loc (unbiased;
+ *   NaN at N = 1), mean_kl = mean of 0.5 (mu^2 + sigma^2 - 1 - log sigma^2); f64 [Z] each. The sums are taken of
+ *   loc - loc[0] (exact in f64), so a common offset of the rows costs no accuracy. ws >=
+ *   svae_latent_colstats_ws_bytes(N, Z).
+ * svae_latent_draw: z = fmaf(scale, eps, loc), f32 [N][Z]; eps f32 [N][Z] or NULL: standard normals from the
+ *   library's counter RNG keyed by (seed, row, column) (Box-Muller of counters 2 (row Z + col) and + 1). */
+#define SVAE_PAIR_RBF 0
+#define SVAE_PAIR_IMQ 1
+#define SVAE_PAIRSUM_TILE_COLS 32
+#define SVAE_PAIRSUM_MAX_P 8
+#define SVAE_MMD_REDUCE_BLOCKS 256
+int svae_pairsum_geometry(int32_t N, int32_t M, int32_t Z, int32_t triangular, int32_t* geom);
+int64_t svae_pairsum_ws_bytes(int32_t N, int32_t M, int32_t Z, int32_t triangular);
+int svae_pairsum(const float* x, int32_t N, const float* y, int32_t M, int32_t Z, int32_t triangular, int32_t kind,
+                 const float* params, int32_t P, const float* col_off, void* ws, int64_t ws_bytes, double* out,
+                 svae_stream_t stream);
+int64_t svae_mmd_rowterm_ws_bytes(int32_t N);
+int svae_mmd_rowterm(const float* x, const float* m, const float* w, int32_t N, int32_t Z, void* ws, int64_t ws_bytes,
+                     double* out, svae_stream_t stream);
+int64_t svae_latent_colstats_ws_bytes(int32_t N, int32_t Z);
+int svae_latent_colstats(const float* loc, const float* scale, int32_t N, int32_t Z, void* ws, int64_t ws_bytes,
+                         double* mean_loc, double* var_loc, double* mean_kl, svae_stream_t stream);
+int svae_latent_draw(const float* loc, const float* scale, const float* eps, uint64_t seed, int32_t N, int32_t Z,
+                     float* z, svae_stream_t stream);
+
 /* library identification: returns a static string (build id, target arch). */
 const char* svae_version(void);
 

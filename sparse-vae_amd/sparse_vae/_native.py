@@ -23,6 +23,9 @@ LATENT_L2, LATENT_COSINE, LATENT_KL = range(3)      # enum svae_latent_metric
 LATENT_METRICS = {'l2': LATENT_L2, 'cosine': LATENT_COSINE, 'kl': LATENT_KL}
 LATENT_MAX_BLOCKS = 1024                             # SVAE_LATENT_MAX_BLOCKS
 TSNE_ROWS_PER_BLOCK, TSNE_TILE_COLS = 512, 256       # SVAE_TSNE_ROWS_PER_BLOCK, SVAE_TSNE_TILE_COLS
+PAIR_RBF, PAIR_IMQ = range(2)                        # SVAE_PAIR_RBF, SVAE_PAIR_IMQ
+PAIR_KINDS = {'rbf': PAIR_RBF, 'imq': PAIR_IMQ}
+PAIRSUM_TILE_COLS, PAIRSUM_MAX_P, MMD_REDUCE_BLOCKS = 32, 8, 256   # SVAE_PAIRSUM_TILE_COLS, _MAX_P, SVAE_MMD_REDUCE_BLOCKS
 
 
 class GemmDesc(ctypes.Structure):
@@ -203,6 +206,16 @@ _SIGS = {
     'svae_tsne_attract': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
     'svae_tsne_update': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_float,
                          c_float, c_void_p],
+    'svae_pairsum_geometry': [c_int32, c_int32, c_int32, c_int32, c_void_p],
+    'svae_pairsum_ws_bytes': [c_int32, c_int32, c_int32, c_int32],
+    'svae_pairsum': [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,
+                     c_void_p, c_int64, c_void_p, c_void_p],
+    'svae_mmd_rowterm_ws_bytes': [c_int32],
+    'svae_mmd_rowterm': [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p],
+    'svae_latent_colstats_ws_bytes': [c_int32, c_int32],
+    'svae_latent_colstats': [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                             c_void_p],
+    'svae_latent_draw': [c_void_p, c_void_p, c_void_p, c_uint64, c_int32, c_int32, c_void_p, c_void_p],
     'svae_version': [],
 }
 
@@ -219,6 +232,8 @@ def _load():
                       'svae_attn_dq_part_elems_w': c_int64, 'svae_attn_fwd_ws_elems': c_int64,
                       'svae_latent_topk_ws_bytes': c_int64,
                       'svae_tsne_repulse_slice_cols': c_int64, 'svae_tsne_repulse_ws_bytes': c_int64,
+                      'svae_pairsum_ws_bytes': c_int64, 'svae_mmd_rowterm_ws_bytes': c_int64,
+                      'svae_latent_colstats_ws_bytes': c_int64,
                       'svae_gemm_group_table_bytes': c_int64}.get(name, ctypes.c_int)
     return lib
 

@@ -1014,3 +1014,100 @@ def tsne_update(y, vel, gains, attr, rep, zsum, exaggeration, learning_rate, mom
     check(lib.svae_tsne_update(y.data_ptr(), vel.data_ptr(), gains.data_ptr(), attr.data_ptr(), rep.data_ptr(),
                                zsum.data_ptr(), n, float(exaggeration), float(learning_rate), float(momentum),
                                stream()), 'svae_tsne_update')
+
+
+def _mmd_rows(t, name):
+    """An [rows, Z] f32 operand of the MMD kernels: contiguous, on the device, Z a multiple of 4 in 4..256."""
+    _dev(t)
+    assert t.dtype == f32 and t.dim() == 2 and t.is_contiguous(), name
+    n, Z = t.shape
+    if Z % 4 or not 4 <= Z <= 256:
+        raise ValueError(f'{name}: the row length must be a multiple of 4 in 4..256, got {Z}')
+    if not 1 <= n <= 2 ** 24:
+        raise ValueError(f'{name}: 1..2^24 rows, got {n}')
+    return n, Z
+
+
+def pairsum_geometry(n, m, Z, triangular):
+    """(rows per workgroup, row blocks, column slices, columns per slice, tile columns) of svae_pairsum."""
+    geom = (ctypes.c_int32 * 5)()
+    check(lib.svae_pairsum_geometry(n, m, Z, int(bool(triangular)), ctypes.addressof(geom)), 'svae_pairsum_geometry')
+    return tuple(geom)
+
+
+def pairsum(x, y=None, *, kind, params, col_off=None, out=None):
+    """svae_pairsum: out f64 [P] = sum over pairs of k_p(|x_i - y_j|^2 + col_off_j). y None: the pairs i < j of x
+    (pdist's); else all pairs of x [N, Z] with y [M, Z]. kind 'rbf': k_p = exp(-params[p] d2); 'imq': k_p =
+    params[p] / (params[p] + d2). params: up to 8 Python floats (rounded to f32). col_off: f32 [M], rectangular only.
+    The per-workgroup workspace is allocated per call (stream-ordered by the caching allocator)."""
+    n, Z = _mmd_rows(x, 'pairsum x')
+    tri = y is None
+    if tri:
+        m = n
+        if n < 2:
+            raise ValueError('pairsum: the triangular set needs at least two rows')
+        if col_off is not None:
+            raise ValueError('pairsum: a column offset only goes with a second set of rows')
+    else:
+        m, Zy = _mmd_rows(y, 'pairsum y')
+        assert Zy == Z, 'x and y differ in row length'
+    params = [float(p) for p in params]
+    P = len(params)
+    if not 1 <= P <= N.PAIRSUM_MAX_P:
+        raise ValueError(f'pairsum: 1..{N.PAIRSUM_MAX_P} kernel parameters, got {P}')
+    if col_off is not None:
+        _dev(col_off)
+        assert col_off.dtype == f32 and col_off.is_contiguous() and col_off.numel() == m
+    dev = x.device
+    out = torch.empty(P, dtype=torch.float64, device=dev) if out is None else out
+    _dev(out)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == P
+    nbytes = lib.svae_pairsum_ws_bytes(n, m, Z, int(tri))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    prm = (ctypes.c_float * P)(*params)
+    check(lib.svae_pairsum(x.data_ptr(), n, None if tri else y.data_ptr(), m, Z, int(tri), N.PAIR_KINDS[kind],
+                           ctypes.addressof(prm), P, ptr(col_off), ws.data_ptr(), nbytes, out.data_ptr(), stream()),
+          'svae_pairsum')
+    return out
+
+
+def mmd_rowterm(x, w, m=None, out=None):
+    """svae_mmd_rowterm: out f64 [1] = sum_i exp(-0.5 sum_j (x_ij - m_j)^2 w_j); w f32 [Z], m f32 [Z] or None (0)."""
+    n, Z = _mmd_rows(x, 'mmd_rowterm x')
+    for t in (w,) if m is None else (w, m):
+        _dev(t)
+        assert t.dtype == f32 and t.is_contiguous() and t.numel() == Z
+    out = torch.empty(1, dtype=torch.float64, device=x.device) if out is None else out
+    _dev(out)
+    assert out.dtype == torch.float64 and out.numel() == 1
+    nbytes = lib.svae_mmd_rowterm_ws_bytes(n)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+    check(lib.svae_mmd_rowterm(x.data_ptr(), ptr(m), w.data_ptr(), n, Z, ws.data_ptr(), nbytes, out.data_ptr(),
+                               stream()), 'svae_mmd_rowterm')
+    return out
+
+
+def latent_colstats(loc, scale):
+    """svae_latent_colstats: (mean_loc, var_loc, mean_kl), f64 [Z] each, over the rows of loc, scale f32 [N, Z]:
+    the mean and unbiased variance of loc and the mean KL to N(0, 1) per latent dimension."""
+    n, Z = _mmd_rows(loc, 'latent_colstats loc')
+    _latent_rows(loc, scale)
+    out = torch.empty(3, Z, dtype=torch.float64, device=loc.device)
+    nbytes = lib.svae_latent_colstats_ws_bytes(n, Z)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=loc.device)
+    check(lib.svae_latent_colstats(loc.data_ptr(), scale.data_ptr(), n, Z, ws.data_ptr(), nbytes, out[0].data_ptr(),
+                                   out[1].data_ptr(), out[2].data_ptr(), stream()), 'svae_latent_colstats')
+    return out[0], out[1], out[2]
+
+
+def latent_draw(loc, scale, seed=0, eps=None, out=None):
+    """svae_latent_draw: z = loc + scale * eps, f32 [N, Z]; eps f32 [N, Z] or None (the counter RNG keyed by seed,
+    row and column)."""
+    n, Z = _mmd_rows(loc, 'latent_draw loc')
+    ts = (loc, scale) if eps is None else (loc, scale, eps)
+    _latent_rows(*ts)
+    out = torch.empty_like(loc) if out is None else out
+    _latent_rows(loc, out)
+    check(lib.svae_latent_draw(loc.data_ptr(), scale.data_ptr(), ptr(eps), int(seed) & (2 ** 64 - 1), n, Z,
+                               out.data_ptr(), stream()), 'svae_latent_draw')
+    return out

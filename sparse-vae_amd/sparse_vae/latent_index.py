@@ -198,6 +198,41 @@ class LatentIndex:
         corpus = self._corpus()
         return K.latent_scores(metric, self._query(query), corpus)
 
+    # ------------------------------------------------------------------ aggregate posterior
+    def stats(self, threshold: float = 0.01):
+        """Per latent dimension over the rows (svae_latent_colstats, f64 [Z] on the device): `mean_loc`, `var_loc`
+        (unbiased) and `mean_kl`, the mean KL(q(z_d|x) || N(0, 1)); `active_units`: the number of dimensions with
+        Var[mu_d] > threshold (Burda et al. 2016); `kl`: the sum of mean_kl (the mean KL term of the ELBO)."""
+        self._corpus()
+        n = self._n
+        mean_loc, var_loc, mean_kl = K.latent_colstats(self._loc[:n], self._scale[:n])
+        return {'mean_loc': mean_loc, 'var_loc': var_loc, 'mean_kl': mean_kl,
+                'active_units': int((var_loc > threshold).sum().item()), 'kl': float(mean_kl.sum().item())}
+
+    def mmd(self, kind: str = 'rbf', source: str = 'sample', seed: int = 0, standardize: bool = True):
+        """MMD^2 between the aggregate posterior and a Gaussian, as a 0-dim f64 tensor on the device. source 'sample':
+        one draw z_i ~ q(z|x_i) per row (svae_latent_draw, counter RNG keyed by `seed`): a sample of the aggregate
+        posterior; 'mean': the posterior means. kind 'rbf': analytic_gaussian_rbf_mmd_sq against N(0, I); 'rbf_fitted':
+        custom_gaussian_rbf_mmd_sq against the diagonal Gaussian with the rows' own mean and variance per dimension
+        (svae_latent_colstats); 'imq': gaussian_imq_mmd_sq (not standardised; its prior samples come from `seed`)."""
+        from .core import math_utils as MU
+        if kind not in ('rbf', 'rbf_fitted', 'imq'):
+            raise ValueError(f"mmd: kind must be 'rbf', 'rbf_fitted' or 'imq', got '{kind}'")
+        if source not in ('sample', 'mean'):
+            raise ValueError(f"mmd: source must be 'sample' or 'mean', got '{source}'")
+        self._corpus()
+        n = self._n
+        if n < 2:
+            raise ValueError('mmd: at least two rows')
+        loc, scale = self._loc[:n], self._scale[:n]
+        z = K.latent_draw(loc, scale, seed=seed) if source == 'sample' else loc
+        if kind == 'rbf':
+            return MU.analytic_gaussian_rbf_mmd_sq(z, standardize)
+        if kind == 'imq':
+            return MU.gaussian_imq_mmd_sq(z, seed=seed)
+        mean, var, _ = K.latent_colstats(z, scale)
+        return MU.custom_gaussian_rbf_mmd_sq(z, mean, var, standardize)
+
     # ------------------------------------------------------------------ persistence
     def save(self, path):
         """One .npz: loc, scale, titles. The derived rows are not stored (load recomputes them)."""
