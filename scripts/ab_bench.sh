@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of bench.py step times: variants alternate (each variant = an env assignment list, e.g.
-# "SVAE_LIB=sparse-vae_amd/sparse_vae/libsvae_old.so" or "SVAE_GEMM_STAGGER=0"; "-" = defaults), optionally after a
-# GPU test subset run with the default library.
+# "SVAE_LIB=sparse-vae_amd/sparse_vae/libsvae_old.so", a build made by build_variant.sh; "-" = defaults), optionally
+# after a GPU test subset run with the default library.
 #   TESTS="tests/test_kernels_gpu.py -k 'gemm or attention'" CFGS="c2 c4" ROUNDS=2 bash scripts/ab_bench.sh TAG VARIANT...
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"

@@ -1,7 +1,7 @@
 """Time the attention backward at the encoder's shapes (64 learned / latent queries over 512 or 1024 keys, hd 64,
 non-causal): one query tile per key block, so each workgroup is mostly prologue and epilogue.
 
-    python scripts/attn_enc_probe.py        (SVAE_ATTN_BWD8=0: the 4-wave 128-key kernel, for A/B)
+    python scripts/attn_enc_probe.py        (compare builds via build_variant.sh + SVAE_LIB)
 """
 import os
 import sys

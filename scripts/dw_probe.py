@@ -1,5 +1,5 @@
-"""Time the weight-gradient GEMMs (C += dY^T X over T tokens) of the C2 step; run under SVAE_GEMM_IMPL=1/2/3 to
-compare kernels. python scripts/dw_probe.py"""
+"""Time the weight-gradient GEMMs (C += dY^T X over T tokens) of the C2 step under the kernel the library picks by
+shape (compare builds via build_variant.sh + SVAE_LIB). python scripts/dw_probe.py"""
 import os
 import sys
 
@@ -31,7 +31,7 @@ for M, N_, K_ in [(512, 512, 32768), (2048, 512, 32768), (1536, 512, 32768), (51
     C = torch.zeros(M, N_, device=dev)
     bg = torch.zeros(M, device=dev)
     t = timeit(lambda: K.linear_dw(dY, X, C, K_, M, N_, bgrad=bg))
-    print(f'impl={os.environ.get("SVAE_GEMM_IMPL", "auto")} dW M={M} N={N_} K={K_} splits={K.auto_splits(M, N_, K_)} '
+    print(f'dW M={M} N={N_} K={K_} splits={K.auto_splits(M, N_, K_)} '
           f'{t:7.1f} us {2.0 * M * N_ * K_ / t / 1e6:7.1f} TF/s', flush=True)
 
 # the two paired launches of the step (FFN1 + FFN2 weight gradients; QKV + out-projection with their bias sums)

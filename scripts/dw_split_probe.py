@@ -42,5 +42,5 @@ for n_out, n_in in [(512, 512), (1024, 512), (1536, 512), (2048, 512), (512, 204
             K.gemm(dY, X, Wg, n_out, n_in, T, a_t=True, b_t=True, lda=n_out, ldb=n_in, ldc=n_in,
                    epi=N.EPI_F32_ATOMIC if s > 1 else N.EPI_F32_ACC, splits=s, aux=slab, a_rowsum=bg)
         us = timeit(fn)
-        print(f'dW{" rs" if RS else ""} impl={os.environ.get("SVAE_GEMM_IMPL", "0")} {n_out}x{n_in} K={T} splits={s:4d}{" (auto)" if s == auto else "       "} {us:8.1f} us '
+        print(f'dW{" rs" if RS else ""} {n_out}x{n_in} K={T} splits={s:4d}{" (auto)" if s == auto else "       "} {us:8.1f} us '
               f'{2.0 * n_out * n_in * T / us / 1e6:7.1f} TF/s', flush=True)

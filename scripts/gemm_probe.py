@@ -104,7 +104,7 @@ if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'epi':
         epi_cases()
         sys.exit(0)
-    print('SVAE_GEMM_GROUP =', os.environ.get('SVAE_GEMM_GROUP'), 'SVAE_GEMM_EXPT =', os.environ.get('SVAE_GEMM_EXPT'))
+    print('library:', os.environ.get('SVAE_LIB', 'default'), '(compare builds via build_variant.sh + SVAE_LIB)')
     head_cases()
     if len(sys.argv) > 1 and sys.argv[1] == 'all':
         shape_cases()

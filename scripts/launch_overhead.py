@@ -2,7 +2,7 @@
 back-to-back launches, for a 1-tile GEMM and the one-tile-per-CU K = 64 / 512 shapes, beside torch memsets.
 With the stamps build the blocks' entry/exit on the 100 MHz clock are printed too.
 
-    SVAE_GEMM_IMPL=3 SVAE_LIB=sparse-vae_amd/sparse_vae/libsvae_stamps.so python scripts/launch_overhead.py
+    SVAE_LIB=sparse-vae_amd/sparse_vae/libsvae_stamps.so python scripts/launch_overhead.py
 """
 import ctypes
 import os

@@ -1,5 +1,5 @@
 """Time the LayerNorm forward alone at the C4 / C5 row shape (65,536 rows x 768, f32 in, bf16 out: 6 B per element)
-and its z-splice form; variants through SVAE_LN_FWD_4COL / SVAE_LN_FWD_BLOCKS. Then the decoder layers' backward at the
+and its z-splice form (compare builds via build_variant.sh + SVAE_LIB). Then the decoder layers' backward at the
 same shapes (dy bf16, x / dres f32 in, dx f32 + bf16 out: 16 B per element) against torch's LayerNorm backward.
 
     python scripts/ln_probe.py

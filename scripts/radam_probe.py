@@ -1,5 +1,5 @@
 """Time the fused clip + RAdam update alone (svae_radam) at the C2 and C4 parameter counts; 30 B per parameter moved
-(read g, m, v, p; write m, v, p, bf16 shadow). Variants through SVAE_RADAM_U / _NT / _GRID.
+(read g, m, v, p; write m, v, p, bf16 shadow); compare builds via build_variant.sh + SVAE_LIB.
 
     python scripts/radam_probe.py
 """

@@ -1,7 +1,7 @@
-"""Time the C2 step's short-K, epilogue-heavy GEMM shapes in isolation under the kernel the library picks (run with
-SVAE_GEMM_IMPL=1|2|3 to force the 128-tile register-staged, the 128-tile LDS-DMA or the 256-tile persistent kernel):
+"""Time the C2 step's short-K, epilogue-heavy GEMM shapes in isolation under the kernel the library picks by shape
+(compare builds via build_variant.sh + SVAE_LIB):
 the out-projection with its f32 residual (one 256 x 256 tile per CU), bf16 out, FFN1 GELU, FFN2 dropout + residual,
-QKV rotary. HIP events, 30 reps.      SVAE_GEMM_IMPL=2 python scripts/shortk_probe.py
+QKV rotary. HIP events, 30 reps.      python scripts/shortk_probe.py
 """
 import os
 import sys
@@ -31,7 +31,6 @@ def timeit(fn, reps=30):
 def main():
     T, d = int(os.environ.get('SHORTK_T', 32768)), 512   # SHORTK_T=4096: the encoder's latent rows (B x 64)
     torch.manual_seed(0)
-    impl = os.environ.get('SVAE_GEMM_IMPL', 'auto')
     x = torch.randn(T, d, device=dev).bfloat16()
     f = torch.randn(T, 4 * d, device=dev).bfloat16()
     w = (torch.randn(d, d, device=dev) * 0.05).bfloat16()
@@ -60,7 +59,7 @@ def main():
     ]
     for name, flop, fn in cases:
         t = timeit(fn)
-        print(f'impl {impl}: {name}: {t:7.1f} us  {flop / t / 1e6:7.1f} TF/s', flush=True)
+        print(f'{name}: {t:7.1f} us  {flop / t / 1e6:7.1f} TF/s', flush=True)
 
 
 if __name__ == '__main__':

@@ -1544,9 +1544,6 @@ __device__ __forceinline__ void bwd_cls_store_slab(const AP& p, float* slab, int
   }
 }
 
-#ifndef SVAE_BWD8_KEYMAP
-#define SVAE_BWD8_KEYMAP 1
-#endif
 template <int HDC, int NSUB, bool RMW>
 __device__ __forceinline__ void attn_bwd8_tile(const AP& p, char* smem, int kb, int h, int b, int nsub) {
   using R = RowImg<HDC>;
@@ -1581,11 +1578,10 @@ __device__ __forceinline__ void attn_bwd8_tile(const AP& p, char* smem, int kb, 
   const bf16* dO = p.dout + b * p.bdo + (long long)h * p.hd;
   const float* lse = p.lse + ((long long)b * p.H + h) * p.Lq;
   const float* delta = p.delta + ((long long)b * p.H + h) * p.Lq;
-  // this wave's 32 keys: slot wk of the block's 8 (SVAE_BWD8_KEYMAP, default 1: waves w and w + 4 -- the two waves of
-  // one SIMD -- take slots w and 7 - w, an early and a late key group, so every SIMD carries the same causal work on
-  // the diagonal key blocks (live query tiles 4 + 1, 4 + 1, 3 + 2, 3 + 2 of a 4-tile sweep, instead of 4 + 2, 4 + 2,
-  // 3 + 1, 3 + 1 with slot = w); 0: slot = w)
-  const int wk = SVAE_BWD8_KEYMAP ? (w < 4 ? w : 11 - w) : w;
+  // this wave's 32 keys: slot wk of the block's 8: waves w and w + 4 -- the two waves of one SIMD -- take slots w and
+  // 7 - w, an early and a late key group, so every SIMD carries the same causal work on the diagonal key blocks (live
+  // query tiles 4 + 1, 4 + 1, 3 + 2, 3 + 2 of a 4-tile sweep, instead of 4 + 2, 4 + 2, 3 + 1, 3 + 1 with slot = w)
+  const int wk = w < 4 ? w : 11 - w;
   const int kw = k0 + 32 * wk;                      // this wave's first key
   bool key_ok[2];
   bf16x8 vf[2][NKK];
@@ -2414,32 +2410,27 @@ bool fill(const svae_attn_desc* d, AP& p) {
 
 // The backward's kernel choice and dQ-partial layout for a shape (svae_attn_bwd and the workspace-size queries agree on
 // it). hd <= 96: the 8-wave 256-key kernel, two 256-key sub-blocks per dQ plane from 512 queries on; hd 128 and the
-// encoder's <= 64 latent queries at hd <= 64: the 4-wave 128-key one. Environment switches (A/B runs only):
-// SVAE_ATTN_BWD8=0 (the 4-wave kernels everywhere), SVAE_ATTN_BWD_SMALLQ=0 (the 8-wave kernel for <= 64 queries too),
-// SVAE_BWD8_SUB=1 (one sub-block per plane), SVAE_ATTN_WINDOW_COMPACT=0 (dense planes in window mode).
+// encoder's <= 64 latent queries at hd <= 64: the 4-wave 128-key one. In window mode the 8-wave kernel's planes are
+// compacted to their band.
 struct BwdLayout {
   bool use8;
   int nsub, kblk, wrows;
   long long plane_elems;   // floats of the dQ partial planes (the [CLS] slabs follow them)
 };
 BwdLayout bwd_layout(int B, int H, int Lq, int Lk, int hd, bool causal, int window) {
-  static const int bwd8_env = [] { const char* e = getenv("SVAE_ATTN_BWD8"); return e ? atoi(e) : 1; }();
   // one query tile (the encoder's 64 latent / learned queries) at hd <= 64: the 4-wave 128-key kernel, two workgroups
   // per CU, hides more of the per-workgroup prologue / epilogue that such a sweep is made of (C2 encoder shape 64 -> 58
   // us, C4's 180 -> 171 us: profiles/r05enc_attn_bwd_smallq_probe.log)
-  static const int smallq_env = [] { const char* e = getenv("SVAE_ATTN_BWD_SMALLQ"); return e ? atoi(e) : 1; }();
+  BwdLayout l;
+  l.use8 = hd <= 96 && !(Lq <= 64 && hd <= 64);
   // two 256-key sub-blocks per workgroup and dQ plane for >= 512 queries; fewer query tiles per key block (the
   // encoder's latent queries) keep one: there the two serial sweeps of one workgroup cost more than the halved planes
-  static const int sub_env = [] { const char* e = getenv("SVAE_BWD8_SUB"); return e && atoi(e) == 1 ? 1 : 2; }();
-  static const int compact_env = [] { const char* e = getenv("SVAE_ATTN_WINDOW_COMPACT"); return e ? atoi(e) : 1; }();
-  BwdLayout l;
-  l.use8 = bwd8_env && hd <= 96 && !(smallq_env && Lq <= 64 && hd <= 64);
-  l.nsub = l.use8 && sub_env == 2 && Lq >= 512 ? 2 : 1;
+  l.nsub = l.use8 && Lq >= 512 ? 2 : 1;
   l.kblk = l.use8 ? BWD8_KEYS * l.nsub : BWD_KEYS;
   const long long D = (long long)H * hd;
   l.wrows = 0;
   l.plane_elems = (long long)((Lk + BWD_KEYS - 1) / BWD_KEYS) * B * Lq * D;   // dense: the 128-key planes (either kernel)
-  if (l.use8 && window > 0 && causal && compact_env) {
+  if (l.use8 && window > 0 && causal) {
     // a plane's band: its keys pk kblk .. + kblk - 1 are seen by queries up to pk kblk + kblk - 32 + 32 window (whole
     // query tiles); plane 0 keeps every row (the [CLS] keys are seen by all queries)
     const int R = (std::min(Lq, l.kblk - SBLK + SBLK * window) + 63) / 64 * 64;
@@ -2467,20 +2458,14 @@ namespace {
 void launch_fwd(const AP& p, hipStream_t s) {
   dim3 grid((p.Lq + 127) / 128, p.H, p.B * p.nsplit);
   const int Lk = p.nsplit > 1 ? p.kc : p.Lk;
-  // the 32x32-MFMA kernel for hd <= 64 (hd 96 spilled; SVAE_ATTN_FWD32=0: the 16x16 kernels, for A/B runs); its padding
-  // bit mask holds FWD32_MAXPAD keys and its DMA / store offsets are 32-bit byte offsets from a sequence's row 0
-  static const int fwd32_env = [] { const char* e = getenv("SVAE_ATTN_FWD32"); return e ? atoi(e) : 1; }();
-  static const int occ_env = [] { const char* e = getenv("SVAE_ATTN_FWD32_OCC"); return e ? atoi(e) : 3; }();
-  static const int ns_env = [] { const char* e = getenv("SVAE_ATTN_FWD32_NS"); return e ? atoi(e) : 2; }();
+  // the 32x32-MFMA kernel for hd <= 64 (hd 96 spilled); its padding bit mask holds FWD32_MAXPAD keys and its DMA /
+  // store offsets are 32-bit byte offsets from a sequence's row 0 (shapes past those limits take the 16x16 kernel)
   const long long so = p.nsplit > 1 ? (long long)p.H * p.hd : p.so, solo = p.nsplit > 1 ? so : p.solo;
   const bool fit32 = ((long long)Lk + 64) * std::max(p.sk, p.sv) * 2 < 0x7FFFFFF0LL &&
                      ((long long)p.Lq + 128) * so * 2 < 0x7FFFFFF0LL && (!p.pad || Lk <= FWD32_MAXPAD) &&
                      (!p.olo || ((long long)p.Lq + 128) * solo * 2 < 0x7FFFFFF0LL);   // (o_lo's 32-bit offsets too)
-  if (fwd32_env && fit32 && p.hd <= 64) {
-    if (ns_env == 3) hipLaunchKernelGGL((attn_fwd32_kernel<64, 3, 3>), grid, dim3(256), 0, s, p);
-    else if (occ_env == 4) hipLaunchKernelGGL((attn_fwd32_kernel<64, 4, 2>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((attn_fwd32_kernel<64, 3, 2>), grid, dim3(256), 0, s, p);
-  } else if (p.hd <= 64) hipLaunchKernelGGL(attn_fwd_kernel<64>, grid, dim3(256), 0, s, p);
+  if (fit32 && p.hd <= 64) hipLaunchKernelGGL((attn_fwd32_kernel<64, 3, 2>), grid, dim3(256), 0, s, p);
+  else if (p.hd <= 64) hipLaunchKernelGGL(attn_fwd_kernel<64>, grid, dim3(256), 0, s, p);
   else if (p.hd <= 96) hipLaunchKernelGGL((attn_fwd_kernel<128, 96>), grid, dim3(256), 0, s, p);
   else hipLaunchKernelGGL(attn_fwd_kernel<128>, grid, dim3(256), 0, s, p);
 }
@@ -2535,16 +2520,13 @@ __global__ __launch_bounds__(256) void attn_fwd_combine_kernel(AP p, const bf16*
   if (c4 == 0) p.lse[lrow] = m + __logf(wsum);
 }
 
-// the split for a shape: slices of kc keys (a multiple of 64), nsplit of them; 1 = no split
+// the split for a shape: slices of kc keys (a multiple of 64), nsplit of them, for about 512 workgroups; 1 = no split
 void fwd_split(int B, int H, int Lq, int Lk, bool causal, int window, int& nsplit, int& kc) {
-  // SVAE_ATTN_FWD_SPLIT: 0 = off, 1 = on (about 512 workgroups), N > 1 = about N workgroups (A/B runs)
-  static const int env = [] { const char* e = getenv("SVAE_ATTN_FWD_SPLIT"); return e ? atoi(e) : 1; }();
   nsplit = 1;
   kc = Lk;
   const long long nwg = (long long)((Lq + 127) / 128) * H * B;
-  if (!env || causal || window > 0 || Lq > 128 || nwg >= 128 || Lk < 2048) return;
-  const long long target = env > 1 ? env : 512;
-  int sp = (int)std::min<long long>((target + nwg - 1) / nwg, (Lk + 255) / 256);
+  if (causal || window > 0 || Lq > 128 || nwg >= 128 || Lk < 2048) return;
+  int sp = (int)std::min<long long>((512 + nwg - 1) / nwg, (Lk + 255) / 256);
   if (sp < 2) return;
   kc = ((Lk + sp - 1) / sp + 63) / 64 * 64;
   nsplit = (Lk + kc - 1) / kc;
@@ -2607,30 +2589,24 @@ SVAE_EXPORT int svae_attn_bwd(const svae_attn_desc* d, svae_stream_t stream) {
   const BwdLayout lay = bwd_layout(d->B, d->H, d->Lq, d->Lk, d->hd, d->causal != 0, d->window);
   const bool use8 = lay.use8;
   const int nsub = lay.nsub;
-  // SVAE_ATTN_DQ_DIRECT=0: every query tile through the partial planes (A/B runs)
-  static const int direct_env = [] { const char* e = getenv("SVAE_ATTN_DQ_DIRECT"); return e ? atoi(e) : 1; }();
   if (use8) {
     p.kblk = lay.kblk;
     p.wrows = lay.wrows;
     // causal: attn_bwd8 stores the final dQ of the queries below dq_direct itself (hd 96: key block 0's, < 256;
     // hd 64 with two sub-blocks: plane 0's, < 512)
-    p.dq_direct = (d->causal && direct_env) ? (nsub == 2 && d->hd <= 64 ? 2 : 1) * BWD8_KEYS : 0;
+    p.dq_direct = d->causal ? (nsub == 2 && d->hd <= 64 ? 2 : 1) * BWD8_KEYS : 0;
     // sliding window: queries from cls_q0 on see nothing of dQ plane 0 but the [CLS] block -> attn_bwd_cls_kernel
-    // (SVAE_ATTN_CLS_SPLIT=0: key block 0 sweeps every query, A/B runs)
-    static const int cls_env = [] { const char* e = getenv("SVAE_ATTN_CLS_SPLIT"); return e ? atoi(e) : 1; }();
-    if (cls_env && d->window > 0 && d->causal && (!d->rot_tab || d->rot_d == d->H * d->hd)) {
+    if (d->window > 0 && d->causal && (!d->rot_tab || d->rot_d == d->H * d->hd)) {
       const int q0 = (std::min(d->Lq, p.kblk - SBLK + SBLK * d->window) + 63) / 64 * 64;
       if (q0 < d->Lq) {
         p.cls_q0 = q0;
         p.cls_part = d->dq_part + lay.plane_elems;
       }
     }
-    // in-kernel delta (SVAE_ATTN_DELTA_INKERNEL=0: the separate pass, A/B runs): the 8-wave kernel at hd <= 64 reads O
-    // and o_lo itself; not with the [CLS] split (attn_bwd_cls_kernel reads delta from memory)
-    static const int dik_env = [] { const char* e = getenv("SVAE_ATTN_DELTA_INKERNEL"); return e ? atoi(e) : 1; }();
+    // in-kernel delta: the 8-wave kernel at hd <= 64 reads O and o_lo itself
     // (with the [CLS] split too: every query row >= cls_q0 lies in the band of the key block holding its own key, whose
     // workgroup stores its delta for attn_bwd_cls_kernel, launched after this kernel on the same stream)
-    if (dik_env && d->hd <= 64 && !d->delta_ready && d->o_lo &&
+    if (d->hd <= 64 && !d->delta_ready && d->o_lo &&
         ((long long)d->Lq + 64) * std::max(d->so, d->so_lo) * 2 < 0x7FFFFFF0LL)
       p.delta_inkernel = 1;
   }
@@ -2652,7 +2628,6 @@ SVAE_EXPORT int svae_attn_bwd(const svae_attn_desc* d, svae_stream_t stream) {
     p.kblk = BWD_KEYS;
     dim3 grid((d->Lk + BWD_KEYS - 1) / BWD_KEYS, d->H, d->B);
     if (d->hd <= 64) hipLaunchKernelGGL(attn_bwd_kernel<64>, grid, dim3(256), 0, s, p);
-    else if (d->hd <= 96) hipLaunchKernelGGL((attn_bwd_kernel<128, 96>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL(attn_bwd_kernel<128>, grid, dim3(256), 0, s, p);
   }
   if (p.cls_q0 > 0) {

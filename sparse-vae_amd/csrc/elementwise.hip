@@ -1323,16 +1323,9 @@ SVAE_EXPORT int svae_radam(float* p, void* pbf, const float* g, float* m, float*
   if (!p || !g || !m || !v || !part || !scal || n <= 0 || n % 4 || nblk <= 0) return SVAE_EINVAL;
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15 || ((uintptr_t)pbf & 7)) return SVAE_EINVAL;
   // the gradient and parameter loads nontemporal as well (C2's 45 M parameters 263 -> 223-227 us; at C4's 162 M all
-  // variants run 4.6-5.0 TB/s: profiles/r05ra_radam_variants.log). SVAE_RADAM_U / _NT / _GRID: A/B variants
-  static const int u_env = [] { const char* e = getenv("SVAE_RADAM_U"); return e ? atoi(e) : 2; }();
-  static const int nt_env = [] { const char* e = getenv("SVAE_RADAM_NT"); return e ? atoi(e) : 1; }();
-  static const int grid_env = [] { const char* e = getenv("SVAE_RADAM_GRID"); return e ? atoi(e) : 2048; }();
-  const dim3 grid(grid_for(n / 4, 256, grid_env)), blk(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (u_env == 4 && nt_env) hipLaunchKernelGGL((radam_kernel<4, true>), grid, blk, 0, s, p, (bf16*)pbf, g, m, v, n, part, nblk, scal, norm_out);
-  else if (u_env == 4) hipLaunchKernelGGL((radam_kernel<4, false>), grid, blk, 0, s, p, (bf16*)pbf, g, m, v, n, part, nblk, scal, norm_out);
-  else if (nt_env) hipLaunchKernelGGL((radam_kernel<2, true>), grid, blk, 0, s, p, (bf16*)pbf, g, m, v, n, part, nblk, scal, norm_out);
-  else hipLaunchKernelGGL((radam_kernel<2, false>), grid, blk, 0, s, p, (bf16*)pbf, g, m, v, n, part, nblk, scal, norm_out);
+  // variants run 4.6-5.0 TB/s: profiles/r05ra_radam_variants.log)
+  hipLaunchKernelGGL((radam_kernel<2, true>), dim3(grid_for(n / 4, 256, 2048)), dim3(256), 0, (hipStream_t)stream, p,
+                     (bf16*)pbf, g, m, v, n, part, nblk, scal, norm_out);
   SVAE_LAUNCH_CHECK();
   return SVAE_OK;
 }

@@ -10,7 +10,6 @@
 // b128 lane groups); M/N-contiguous tiles with ds_read_b64_tr_b16 (XOR-swizzled 8-B units).
 #include "common.h"
 #include "../../include/svae.h"
-#include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -1187,11 +1186,8 @@ __device__ unsigned long long svae_rt[1024][2];   // per block: entry, exit (s_m
 #else
 #define G3_STAMP(k) ((void)0)
 #endif
-#ifndef SVAE_KW_FORM
-#define SVAE_KW_FORM 0
-#endif
 #ifndef SVAE_KW_PRE
-#define SVAE_KW_PRE 1   // form 0's weights loaded at the K-tile top by counted asm loads (0: at the use, no DMA stagger)
+#define SVAE_KW_PRE 1   // the k-weights loaded at the K-tile top by counted asm loads (0: at the use, no DMA stagger)
 #endif
 
 // Vector-memory operations every wave issues unconditionally in the epilogue of an interior 256 x 256 tile (stores
@@ -1231,18 +1227,8 @@ __device__ __forceinline__ void gemm256_run(const GP& p, int blk, int nwg, bool 
   // 2 ring stages + a side area: the epilogue's per-tile bias (256 f32), CE labels (256 i32) and CE row statistics
   // ([256 rows][4 column waves][max, sum]); one array
   static_assert(g3_epi_vmem_ops<EPI>() >= G3_EPI_STORES, "the relaxed first wait would not cover the prefetch DMA");
-  // ACC_KW with SVAE_KW_FORM > 0 (diagnostic builds; the product, form 0, loads the weights from global memory):
-  // [stage][wave] k-weight slots, each wave DMAs the weights of a K-tile into its OWN slot -- form 1: 64 dwords
-  // (buffer_load_dword lds) after the side area (138 KiB); form 2: 16-B pieces (buffer_load_dwordx4 lds, lanes 0-15)
-  // after the side area; form 3: 64 dwords at offset 0, the ring moved up by 4 KiB (all DMA below 132 KiB)
-  constexpr bool IS_KW = EPI == G3_EPI_ACC_KW || EPI == G3_EPI_F32_KW;
-  constexpr int KW_FORM = IS_KW ? SVAE_KW_FORM : 0;
-  constexpr int KW_SLOT = KW_FORM == 2 ? 1024 : 256;
-  constexpr int KW_BYTES = KW_FORM ? 2 * 8 * KW_SLOT : 0;
-  constexpr int RING_OFF = KW_FORM == 3 ? KW_BYTES : 0;
-  constexpr int KW_OFF = KW_FORM == 3 ? 0 : 2 * G3_STAGE + 2048 + 8192;
-  __shared__ __attribute__((aligned(16))) char smem[2 * G3_STAGE + 2048 + 8192 + KW_BYTES];
-  char* ring = smem + RING_OFF;
+  constexpr bool IS_KW = EPI == G3_EPI_ACC_KW || EPI == G3_EPI_F32_KW;   // (the k-weights come from global memory)
+  __shared__ __attribute__((aligned(16))) char ring[2 * G3_STAGE + 2048 + 8192];
   float* sbias = (float*)(ring + 2 * G3_STAGE);
   int* slabel = (int*)(ring + 2 * G3_STAGE + 1024);
   float* sstat = (float*)(ring + 2 * G3_STAGE + 2048);
@@ -1261,26 +1247,9 @@ __device__ __forceinline__ void gemm256_run(const GP& p, int blk, int nwg, bool 
   int t3 = bid;
   if (t3 >= p.total3) return;
   G3Tile T = g3_tile(p, t3);
-  // ACC_KW: the 64 k-weights of a K-tile ride along with its operand pieces, one dword per lane into this wave's own
-  // slot of the K-tile's stage; read after the same counted wait + barrier as the operands (no cross-wave hand-off)
-  char* skw = smem + KW_OFF;
-  auto kw_issue = [&](int k0, int kend, int stage) {
-    if constexpr (KW_FORM == 1 || KW_FORM == 3) {
-      const u32x4 kwr = buffer_rsrc(p.k_weight, 0x7FFFFFF0u);
-      const int kk = k0 + lane_id_fresh();
-      dma4_lds(kwr, skw + (stage * 8 + wave) * KW_SLOT, kk < kend ? kk * 4 : 0x7FFFFFF0);
-    } else if constexpr (KW_FORM == 2) {
-      const u32x4 kwr = buffer_rsrc(p.k_weight, 0x7FFFFFF0u);
-      const int l = lane_id_fresh(), kk = k0 + 4 * l;
-      dma16_lds(kwr, skw + (stage * 8 + wave) * KW_SLOT, l < 16 && kk < kend ? kk * 4 : 0x7FFFFFF0);
-    }
-  };
   const G3Src sa = g3_src<AT>(p.lda, wave, lane), sb = g3_src<BT>(p.ldb, wave, lane);
   int g = 0;   // K-tiles consumed so far by this block: the stage of K-tile g is g & 1
-  if (T.nk > 0) {
-    g3_issue<AT, BT>(p, T.A, T.B, sa, sb, T.m0, T.n0, T.kbeg, T.kend, ring, wave);
-    kw_issue(T.kbeg, T.kend, 0);
-  }
+  if (T.nk > 0) g3_issue<AT, BT>(p, T.A, T.B, sa, sb, T.m0, T.n0, T.kbeg, T.kend, ring, wave);
 
   bool relaxed = false;   // the previous tile was interior: its epilogue issued >= G3_EPI_STORES stores per wave
   int ntile = 0;
@@ -1310,16 +1279,14 @@ __device__ __forceinline__ void gemm256_run(const GP& p, int blk, int nwg, bool 
       const bool do_rs = AT && p.a_rowsum && T.bn < 2;
       // p.dma_stagger: the two waves of a SIMD (wr 0 and 1, same wc) issue their pieces of the next K-tile at different
       // times -- wr 0 here, wr 1 after its first MFMA quadrant -- so one wave's DMA issue runs beside the other's MFMAs
-      // (the k-weighted forms: form 0 loads the weights from global memory at the use, whose wait would also wait for
-      // the late pieces, so no stagger; the LDS-slot diagnostic forms stagger)
-      // ACC_KW form 0: the K-tile's 64 weights are loaded here, one dword per lane, BEFORE this K-tile's 8 DMA pieces
+      // ACC_KW: the K-tile's 64 weights are loaded here, one dword per lane, BEFORE this K-tile's 8 DMA pieces
       // (issued next, or after the first quadrant by a late wave; the block's very last K-tile issues 8 out-of-range
       // pieces instead, so the count holds), by an asm buffer load the compiler does not track; the use waits vmcnt(8)
       // -- those pieces may stay in flight, so the DMA stagger applies to the k-weighted GEMM too -- and takes each
       // lane's 8 weights of a k-step by ds_bpermute (1 VGPR live across the quadrants instead of 8 or 16; a
       // compiler-visible load made hipcc wait vmcnt(0), draining the DMA, and the wider live forms spilled)
       const int ks0 = p.tn2 >= 2 ? T.bn : 0, ks1 = p.tn2 >= 2 ? T.bn + 1 : 2;
-      const bool kw_pre = IS_KW && KW_FORM == 0 && SVAE_KW_PRE && do_rs;   // (block-uniform)
+      const bool kw_pre = IS_KW && SVAE_KW_PRE && do_rs;   // (block-uniform)
       float kw1 = 0.f;
       if (kw_pre) {
         const int kk = T.kbeg + kt * 64 + lane_id_fresh();
@@ -1327,14 +1294,12 @@ __device__ __forceinline__ void gemm256_run(const GP& p, int blk, int nwg, bool 
         const u32x4 kwr = buffer_rsrc(p.k_weight, 0x7FFFFFF0u);
         asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, 0 offen" : "=&v"(kw1) : "v"(off), "s"(kwr) : "memory");
       }
-      const bool late = (!IS_KW || KW_FORM > 0 || kw_pre) && p.dma_stagger && wr == 1 && kt + 1 < T.nk;   // (uniform)
+      const bool late = (!IS_KW || kw_pre) && p.dma_stagger && wr == 1 && kt + 1 < T.nk;   // (uniform)
       if (kt + 1 < T.nk) {
         if (!late) g3_issue<AT, BT>(p, T.A, T.B, sa, sb, T.m0, T.n0, T.kbeg + (kt + 1) * 64, T.kend, nxt, wave);
-        kw_issue(T.kbeg + (kt + 1) * 64, T.kend, (g + 1) & 1);   // (every wave here, late or not)
       } else if (next_dma) {   // the next tile's first K-tile, in flight during this tile's epilogue
         const G3Tile TN = g3_tile(p, t3n);
         g3_issue<AT, BT>(p, TN.A, TN.B, sa, sb, TN.m0, TN.n0, TN.kbeg, TN.kend, nxt, wave);
-        kw_issue(TN.kbeg, TN.kend, (g + 1) & 1);
       } else if (kw_pre) {   // (see kw_pre: 8 pieces that read nothing, into the idle stage)
         const u32x4 rs = buffer_rsrc(p.A, 0x7FFFFFF0u);
 #pragma unroll
@@ -1349,20 +1314,15 @@ __device__ __forceinline__ void gemm256_run(const GP& p, int blk, int nwg, bool 
       // 2 wc, 2 wc + 1 of its wave row's eight (balanced over the SIMDs; a0's right after their last MFMA use),
       // summed over the lane groups at the end of the tile. ACC_KW: the lane's 8 weights per k-step are global loads
       // at the use (L2-resident; the compiler's wait for them also drains the next K-tile's DMA pieces issued before
-      // them). Every LDS form measured (a ring filled by wave 0; each wave's own slot DMA'd with the K-tile's pieces,
-      // forms 1-3 of SVAE_KW_FORM, kept for diagnostic builds) read stale weights now and then in the bit-exact test
-      // (DESIGN §6); registers loaded a K-tile ahead spilled (34 VGPRs). The first two column tiles (blocks bn = 0, 1
+      // them). Every LDS form measured (a ring filled by wave 0; each wave's own slot DMA'd with the K-tile's pieces)
+      // read stale weights now and then in the bit-exact test; registers loaded a K-tile ahead spilled (34 VGPRs). The first two column tiles (blocks bn = 0, 1
       // hold the same A rows) split the work by k-step, so neither runs much longer than the blocks without row sums.
       auto rowsum2 = [&](const bf16x8 (&x)[2], const bf16x8 (&y)[2]) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           if (ks < ks0 || ks >= ks1) continue;   // (block-uniform)
           f32x4 k0 = {1.f, 1.f, 1.f, 1.f}, k1 = k0;
-          if constexpr (KW_FORM > 0) {   // this wave's slot of the stage (zeros past kend)
-            const float* kws = (const float*)(skw + ((g & 1) * 8 + wave) * KW_SLOT) + 32 * ks + 8 * (lane >> 4);
-            k0 = *(const f32x4*)kws;
-            k1 = *(const f32x4*)(kws + 4);
-          } else if constexpr (IS_KW) {
+          if constexpr (IS_KW) {
             if (kw_pre) {   // (kw1 landed: the wait after the second quadrant)
               const int src0 = (32 * ks + 8 * (lane_id_fresh() >> 4)) * 4;
 #pragma unroll
@@ -1501,10 +1461,8 @@ __device__ __forceinline__ void gemm256_run(const GP& p, int blk, int nwg, bool 
     const bool prefetched = T.nk > 0;
     t3 = t3n;
     T = g3_tile(p, t3);
-    if (!prefetched && T.nk > 0) {   // (an empty split-K slice prefetched nothing)
+    if (!prefetched && T.nk > 0)   // (an empty split-K slice prefetched nothing)
       g3_issue<AT, BT>(p, T.A, T.B, sa, sb, T.m0, T.n0, T.kbeg, T.kend, ring + (g & 1) * G3_STAGE, wave);
-      kw_issue(T.kbeg, T.kend, g & 1);
-    }
   }
 }
 
@@ -1851,9 +1809,8 @@ static int gemm_run(const svae_gemm_desc* d, svae_stream_t stream, bool* fused_d
   if (nblocks > 0x7FFFFFFF) return SVAE_EINVAL;
   dim3 grid((unsigned)nblocks);
   hipStream_t s = (hipStream_t)stream;
-  // M <= 64 (one row per sequence): the skinny kernel (SVAE_GEMM_SKINNY=0 turns it off for A/B runs)
-  static const int skinny_env = [] { const char* e = getenv("SVAE_GEMM_SKINNY"); return e ? atoi(e) : 1; }();
-  if (skinny_env && d->M <= 64 && !d->a_t && !d->b_t && d->batch == 1 && d->splits == 1 && !d->a_rowsum &&
+  // M <= 64 (one row per sequence): the skinny kernel
+  if (d->M <= 64 && !d->a_t && !d->b_t && d->batch == 1 && d->splits == 1 && !d->a_rowsum &&
       d->C && d->K % 8 == 0 && d->lda % 8 == 0 && d->ldb % 8 == 0 && ((uintptr_t)d->A & 15) == 0 &&
       ((uintptr_t)d->B & 15) == 0 &&
       (d->epi == SVAE_EPI_BF16 || d->epi == SVAE_EPI_F32 || d->epi == SVAE_EPI_GELU || d->epi == SVAE_EPI_GELU_BWD ||
@@ -1871,22 +1828,20 @@ static int gemm_run(const svae_gemm_desc* d, svae_stream_t stream, bool* fused_d
   }
   const int lay = (d->a_t ? 2 : 0) | (d->b_t ? 1 : 0);
   // short-K GEMMs: the 3-stage LDS-DMA kernel (3 blocks/CU overlap prologues/epilogues); long-K GEMMs: the
-  // BK=64 register-staged kernel (half the barriers per MFMA). SVAE_GEMM_IMPL=1/2 forces one (A/B runs).
-  static const int forced = [] { const char* e = getenv("SVAE_GEMM_IMPL"); return e ? atoi(e) : 0; }();
+  // BK=64 register-staged kernel (half the barriers per MFMA).
   const int kslice = (d->K + d->splits - 1) / d->splits;
   p.tn2 = (d->N + 255) / 256;
   p.tm2 = (d->M + 255) / 256;
-  static const int group_env = [] { const char* e = getenv("SVAE_GEMM_GROUP"); return e ? atoi(e) : -1; }();
   // wide N (the vocab head, 128 column tiles): groups of 4 tile rows, so each XCD's 32 concurrent tiles are 4 rows x
   // 8 columns (12 operand strips in its L2 instead of 33): head fwd 1385 -> 1314 us (scripts/gemm_probe.py). No
   // effect measured on the narrow (<= 8 column tiles) C2 shapes.
-  p.group = group_env >= 0 ? group_env : (p.tn2 >= 32 ? 4 : 0);
+  p.group = p.tn2 >= 32 ? 4 : 0;
   const long long blocks256 = (long long)p.tn2 * p.tm2 * d->batch * d->splits;
   // (a_t with a K-contiguous B: the gemm256 copy exists for the f32-accumulate epilogues only -- the vocabulary head's
   // dW with a transposed B operand)
   const bool acc_epi = d->epi == SVAE_EPI_F32_ACC;
   const bool ok3 = !(d->a_t && !d->b_t) || acc_epi;
-  int impl = forced ? forced : ((ok3 && blocks256 >= 192) ? 3 : ((kslice <= 2048 && !(d->a_t && d->b_t)) ? 2 : 1));
+  int impl = (ok3 && blocks256 >= 192) ? 3 : ((kslice <= 2048 && !(d->a_t && d->b_t)) ? 2 : 1);
   if (epi_new || d->k_weight || (d->a_t && !d->b_t && acc_epi && blocks256 >= 192)) impl = 3;
   if (d->k_weight) {
     if (d->epi == SVAE_EPI_F32_ACC && d->splits == 1) epi_run = G3_EPI_ACC_KW;
@@ -1903,8 +1858,7 @@ static int gemm_run(const svae_gemm_desc* d, svae_stream_t stream, bool* fused_d
     int kc3 = (d->K + d->splits - 1) / d->splits;
     p.kchunk = (kc3 + 63) / 64 * 64;
     // persistent above one block per CU (1 block of 8 waves fits a CU): blocks walk their tiles and prefetch the
-    // next tile's first K-tile under the current tile's epilogue. SVAE_GEMM_PERSIST=0 restores 1 block per tile.
-    static const int persist_env = [] { const char* e = getenv("SVAE_GEMM_PERSIST"); return e ? atoi(e) : 1; }();
+    // next tile's first K-tile under the current tile's epilogue.
     static const int ncu = [] {
       int dev = 0, n = 0;
       if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -1912,13 +1866,11 @@ static int gemm_run(const svae_gemm_desc* d, svae_stream_t stream, bool* fused_d
       return n > 0 ? n : 256;
     }();
     p.total3 = (int)blocks256;
-    const long long nb3 = persist_env ? std::min<long long>(blocks256, ncu) : blocks256;
-    static const int relax_env = [] { const char* e = getenv("SVAE_GEMM_RELAX"); return e ? atoi(e) : 1; }();
+    const long long nb3 = std::min<long long>(blocks256, ncu);
     // (the CE-statistics epilogue without a logits store issues too few stores for the counted first wait)
-    p.relaxed = relax_env && !(d->epi == SVAE_EPI_CE_STATS && !d->C);
-    // (SVAE_GEMM_STAGGER=0 for A/B: C2 step 12.89 / 12.99 -> 12.75 / 12.73 ms, head forward 1.12 -> 1.07 ms)
-    static const int stagger_env = [] { const char* e = getenv("SVAE_GEMM_STAGGER"); return e ? atoi(e) : 1; }();
-    p.dma_stagger = stagger_env;
+    p.relaxed = !(d->epi == SVAE_EPI_CE_STATS && !d->C);
+    // (staggered DMA issue: C2 step 12.89 / 12.99 -> 12.75 / 12.73 ms, head forward 1.12 -> 1.07 ms)
+    p.dma_stagger = 1;
     dim3 grid3((unsigned)nb3);
     // the delta epilogue (a wave's 64 columns hold at most two heads: hd >= 64) adds into a zeroed delta (svae_gemm)
     if (fused_delta && epi_run == SVAE_EPI_BF16 && d->delta_hd >= 64) {
@@ -2052,11 +2004,6 @@ SVAE_EXPORT int svae_gemm_pair(const svae_gemm_desc* d0, const svae_gemm_desc* d
   hipLaunchKernelGGL((gemm256_pair_kernel<true, true, G3_EPI_SLAB>), dim3((unsigned)(q.nb0 + nb[1])), dim3(512), 0, s,
                      q);
   SVAE_LAUNCH_CHECK();
-  static const int two_env = [] { const char* e = getenv("SVAE_SLAB2"); return e ? atoi(e) : 1; }();
-  if (!two_env) {   // (A/B: one launch per GEMM)
-    if (const int rc = launch_slab_reduce(d0, s)) return rc;
-    return launch_slab_reduce(d1, s);
-  }
   const long long b0 = slab_blocks(d0), b1 = slab_blocks(d1);
   hipLaunchKernelGGL(slab_reduce2_kernel, dim3((unsigned)(b0 + b1)), dim3(256), 0, s, slab_red(d0), slab_red(d1), (int)b0);
   SVAE_LAUNCH_CHECK();

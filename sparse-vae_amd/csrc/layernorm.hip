@@ -5,7 +5,6 @@
 // output head (transformer_language_model.py:59). HBM-bound: forward moves 4d (f32 in) + 2d (bf16 out)
 // bytes per row; backward reads dy (2d), x (4d), dres (4d) and writes dx (4d + 2d).
 #include <algorithm>
-#include <cstdlib>
 
 #include "common.h"
 #include "../../include/svae.h"
@@ -641,17 +640,30 @@ SVAE_EXPORT int svae_colsum_multi(const svae_colsum_seg* segs, int32_t n, svae_s
   return SVAE_OK;
 }
 
+// The forward's grid and row layout for (rows, D), shared by svae_layernorm_fwd, _fwd_z and _fwd_multi (so their
+// outputs are bit-identical). Rows per wave: the grid holds at most 2048 blocks of 4 waves for D <= 768, 1024 above
+// (where 2048 measured slower with the 8-column layout). MV, the kernels' MAXV: even = the 8-column layout, which
+// needs D % 8 == 0 and 16-B aligned rows. The 4-column layout (3) for 512 < D <= 768: every lane busy in every run;
+// with 2048 blocks the C4 / C5 row shape runs 59.7 -> 55.5 us, its z-splice form 76 -> 62.6 us
+// (profiles/r05ln_ln_fwd_probe.log). Round 5 kept it off because its other fp32 summation order moved an encoder
+// k_linear weight gradient's norm ratio to 0.979 against a 2 % bar; that bar sat inside the bf16 noise floor of those
+// gradients (sigma 1.4-2.0 %, tests/golden/noise_floor_c4shape.json), and on that floor the 4-column build is no less
+// accurate: norm-ratio deviations rms 0.56-0.79 sigma against 0.61-0.98 for the 8-column one over the C2 / C4 / C5
+// step-parity cases (profiles/r06m_ln4col_parity.log).
+struct LnFwdPlan {
+  unsigned grid;
+  int mv;
+};
+static LnFwdPlan ln_fwd_plan(int rows, int D) {
+  const int mv = (D % 8 == 0 && D <= 512) ? 2 : D <= 768 ? 3 : D % 8 == 0 ? 4 : 5;
+  return {(unsigned)std::min((rows + 3) / 4, D <= 768 ? 2048 : 1024), mv};
+}
+
 SVAE_EXPORT int svae_layernorm_fwd(const void* x, int32_t x_dtype, const float* w, const float* b, void* y,
                                    float* mean, float* rstd, int32_t rows, int32_t D, svae_stream_t stream) {
   if (!x || !w || !b || !y || !mean || !rstd || rows <= 0 || D <= 0 || D % 4 || D > 1024) return SVAE_EINVAL;
-  // rows per wave: the grid holds at most SVAE_LN_FWD_BLOCKS blocks of 4 waves (0: one row per wave)
-  // (default: 2048 blocks for D <= 512, 1024 above -- where 2048 measured slower with the 8-column layout)
-  static const int cap_env = [] { const char* e = getenv("SVAE_LN_FWD_BLOCKS"); return e ? atoi(e) : -1; }();
-  static const int c4 = [] { const char* e = getenv("SVAE_LN_FWD_4COL"); return e ? atoi(e) : 1; }();
-  // (the 4-column layout at 512 < D <= 768 runs 2048 blocks too)
-  const int cap = cap_env >= 0 ? cap_env : ((D <= 512 || (c4 && D <= 768)) ? 2048 : 1024);
-  const int need = (rows + 3) / 4;
-  dim3 grid((unsigned)(cap > 0 ? std::min(need, cap) : need));
+  const LnFwdPlan plan = ln_fwd_plan(rows, D);
+  const dim3 grid(plan.grid);
   hipStream_t s = (hipStream_t)stream;
 #define SVAE_LN_FWD(MV)                                                                                            \
   do {                                                                                                             \
@@ -662,17 +674,9 @@ SVAE_EXPORT int svae_layernorm_fwd(const void* x, int32_t x_dtype, const float* 
       hipLaunchKernelGGL((ln_fwd_kernel<bf16, MV>), grid, dim3(256), 0, s, (const bf16*)x, w, b, (bf16*)y, mean,   \
                          rstd, rows, D);                                                                           \
   } while (0)
-  // (even MAXV = the 8-column layout, which needs D % 8 == 0 and 16-B aligned rows. The 4-column layout for 512 < D <=
-  // 768 (SVAE_LN_FWD_4COL=0 turns it off): every lane busy in every run; with 2048 blocks the C4 / C5 row shape runs
-  // 59.7 -> 55.5 us, its z-splice form 76 -> 62.6 us (profiles/r05ln_ln_fwd_probe.log). Round 5 kept it off because its
-  // other fp32 summation order moved an encoder k_linear weight gradient's norm ratio to 0.979 against a 2 % bar; that bar
-  // sat inside the bf16 noise floor of those gradients (sigma 1.4-2.0 %, tests/golden/noise_floor_c4shape.json), and on
-  // that floor the 4-column build is no less accurate: norm-ratio deviations rms 0.56-0.79 sigma against 0.61-0.98 for
-  // the 8-column one over the C2 / C4 / C5 step-parity cases (profiles/r06m_ln4col_parity.log))
-  if (c4 && D > 512 && D <= 768) SVAE_LN_FWD(3);
-  else if (D % 8 == 0 && D <= 512) SVAE_LN_FWD(2);
-  else if (D % 8 == 0) SVAE_LN_FWD(4);
-  else if (D <= 768) SVAE_LN_FWD(3);
+  if (plan.mv == 2) SVAE_LN_FWD(2);
+  else if (plan.mv == 3) SVAE_LN_FWD(3);
+  else if (plan.mv == 4) SVAE_LN_FWD(4);
   else SVAE_LN_FWD(5);
 #undef SVAE_LN_FWD
   SVAE_LAUNCH_CHECK();
@@ -684,18 +688,13 @@ SVAE_EXPORT int svae_layernorm_fwd_z(float* x, const float* zrows, int32_t zmod,
   if (!x || !zrows || zmod <= 0 || !w || !b || !y || !mean || !rstd || rows <= 0 || D <= 0 || D % 8 || D > 1024)
     return SVAE_EINVAL;
   if (((uintptr_t)x | (uintptr_t)zrows) & 15) return SVAE_EINVAL;
-  // (default: 2048 blocks for D <= 512, 1024 above -- where 2048 measured slower with the 8-column layout)
-  static const int cap_env = [] { const char* e = getenv("SVAE_LN_FWD_BLOCKS"); return e ? atoi(e) : -1; }();
-  static const int c4 = [] { const char* e = getenv("SVAE_LN_FWD_4COL"); return e ? atoi(e) : 1; }();
-  // (the 4-column layout at 512 < D <= 768 runs 2048 blocks too)
-  const int cap = cap_env >= 0 ? cap_env : ((D <= 512 || (c4 && D <= 768)) ? 2048 : 1024);
-  const int need = (rows + 3) / 4;
-  dim3 grid((unsigned)(cap > 0 ? std::min(need, cap) : need));
+  const LnFwdPlan plan = ln_fwd_plan(rows, D);   // (D % 8 == 0: 2, 3 or 4)
+  const dim3 grid(plan.grid);
   hipStream_t s = (hipStream_t)stream;
-  if (D <= 512)
+  if (plan.mv == 2)
     hipLaunchKernelGGL((ln_fwd_kernel<float, 2, true>), grid, dim3(256), 0, s, (const float*)x, w, b, (bf16*)y, mean,
                        rstd, rows, D, zrows, zmod, x);
-  else if (c4 && D <= 768)
+  else if (plan.mv == 3)
     hipLaunchKernelGGL((ln_fwd_kernel<float, 3, true>), grid, dim3(256), 0, s, (const float*)x, w, b, (bf16*)y, mean,
                        rstd, rows, D, zrows, zmod, x);
   else
@@ -744,18 +743,13 @@ SVAE_EXPORT int svae_layernorm_fwd_multi(const float* x, const float* const* w, 
     if (!w[i] || !b[i] || !y[i]) return SVAE_EINVAL;
     m.w[i] = w[i]; m.b[i] = b[i]; m.y[i] = (bf16*)y[i];
   }
-  // the grid and the row layout of svae_layernorm_fwd (so the outputs are bit-identical to its)
-  static const int cap_env = [] { const char* e = getenv("SVAE_LN_FWD_BLOCKS"); return e ? atoi(e) : -1; }();
-  static const int c4 = [] { const char* e = getenv("SVAE_LN_FWD_4COL"); return e ? atoi(e) : 1; }();
-  const int cap = cap_env >= 0 ? cap_env : ((D <= 512 || (c4 && D <= 768)) ? 2048 : 1024);
-  const int need = (rows + 3) / 4;
-  dim3 grid((unsigned)(cap > 0 ? std::min(need, cap) : need));
+  const LnFwdPlan plan = ln_fwd_plan(rows, D);
+  const dim3 grid(plan.grid);
   hipStream_t s = (hipStream_t)stream;
 #define SVAE_LN_FWDM(MV) hipLaunchKernelGGL((ln_fwd_multi_kernel<MV>), grid, dim3(256), 0, s, x, m, mean, rstd, rows, D)
-  if (c4 && D > 512 && D <= 768) SVAE_LN_FWDM(3);
-  else if (D % 8 == 0 && D <= 512) SVAE_LN_FWDM(2);
-  else if (D % 8 == 0) SVAE_LN_FWDM(4);
-  else if (D <= 768) SVAE_LN_FWDM(3);
+  if (plan.mv == 2) SVAE_LN_FWDM(2);
+  else if (plan.mv == 3) SVAE_LN_FWDM(3);
+  else if (plan.mv == 4) SVAE_LN_FWDM(4);
   else SVAE_LN_FWDM(5);
 #undef SVAE_LN_FWDM
   SVAE_LAUNCH_CHECK();

@@ -146,3 +146,12 @@ def test_zproj_fwd_seg_layout():
     from sparse_vae import _native as N
     assert ctypes.sizeof(N.ZprojFwdSeg) == 24
     assert [f[0] for f in N.ZprojFwdSeg._fields_] == ['W', 'bias', 'out']
+
+
+def test_library_reads_no_environment():
+    """What a library call launches depends on its arguments alone: no source under csrc reads the environment."""
+    csrc = os.path.join(ROOT, 'sparse-vae_amd', 'csrc')
+    names = sorted(os.listdir(csrc))
+    assert any(n.endswith('.hip') for n in names)
+    readers = [n for n in names if 'getenv' in open(os.path.join(csrc, n), errors='replace').read()]
+    assert not readers, readers

@@ -3,7 +3,6 @@ svae_reparam_kl_fwd / _bwd, the embedding gather / scatter) at the sizes where t
 float64 restatements of tests/optim_ref.py. The bounds are optim_ref's: 4 x the f32-vs-f64 deviation of the same
 formulas, measured on the CPU by test_optim_ref.py on these inputs. Every output buffer carries 64 guard elements."""
 import math
-import os
 
 import numpy as np
 import pytest
@@ -100,12 +99,6 @@ def test_sumsq_randn_at_the_training_pair():
 
 
 # ================================================================================================ radam
-def _default_radam_variant():
-    """svae_radam reads SVAE_RADAM_U / _NT / _GRID once per process; these tests are about the default kernel."""
-    knobs = [k for k in ('SVAE_RADAM_U', 'SVAE_RADAM_NT', 'SVAE_RADAM_GRID') if k in os.environ]
-    assert not knobs, f'{knobs} set in the environment: this run would test another RAdam variant than the default'
-
-
 @pytest.mark.parametrize('rho_ok', [0, 1])
 @pytest.mark.parametrize('clip_active', [True, False])
 @pytest.mark.parametrize('n', R.RADAM_SIZES)
@@ -114,7 +107,6 @@ def test_radam_three_steps_elementwise(n, clip_active, rho_ok):
     n = 4, 1020, 10000: n / 4 <= 2048 * 256, every thread at most one vector, in the tail loop. n = 5 243 028
     (n / 4 = 2 * 524288 + 262181, 2048 blocks): every thread one trip of the 2-way unrolled main loop, threads
     below 262181 one tail trip more. The 1024 partials (a real svae_sumsq) take the partial-sum loop four trips."""
-    _default_radam_variant()
     p0, m0, v0, gs, scals = R.radam_case(n, clip_active, rho_ok, dev)
     max_norm = scals[0][8].item()
     bufs = {k: guarded(t) for k, t in (('p', p0), ('m', m0), ('v', v0), ('p2', p0), ('m2', m0), ('v2', v0))}
