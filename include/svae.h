@@ -420,8 +420,14 @@ int svae_clip_grad(float* g, int64_t n, const float* part, int32_t nblk, float m
 
 /* ---- fp32 kernel mode (argmax-reconstruction parity; TransformerVAE.reconstruct in exact f32) ---------
  * svae_gemm_f32: C[M,N] = epi(A[M,K] . W[N,K]^T) on f32-input MFMA; epi in {SVAE_EPI_F32 (+bias, +resid),
- * SVAE_EPI_ROTARY_BF16 (rotary on cols < rot_cols, f32 out), SVAE_EPI_GELU (f32 out)}.
- * svae_attn_fwd_f32: attention forward in f32 (same strides / masks / window as svae_attn_desc).
+ * SVAE_EPI_ROTARY_BF16 (rotary on cols < rot_cols, f32 out), SVAE_EPI_GELU (f32 out)}: these three and no other
+ * (SVAE_EINVAL otherwise). bias and resid (added after the epilogue's function) are optional with each. Any M, N,
+ * K >= 1 and any leading dimensions in elements; no alignment is required. The rotary epilogue needs rot_tab,
+ * rot_d > 0, rot_seq > 0 and an even rot_cols (pairs of adjacent columns rotate together); row m takes table row
+ * m % rot_seq.
+ * svae_attn_fwd_f32: attention forward in f32 (same strides / masks / window as svae_attn_desc). Lk <= 32768 (a
+ * query's scores for every key are held in LDS); window > 0 requires causal (the block-sparse band is causal).
+ * SVAE_EINVAL otherwise. Any hd >= 1.
  * svae_layernorm_fwd_f32: LayerNorm with f32 output. */
 int svae_gemm_f32(const float* A, const float* W, float* C, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldw,
                   int64_t ldc, const float* bias, const float* resid, int64_t ldr, int32_t epi, const float* rot_tab,
@@ -436,14 +442,17 @@ int svae_layernorm_fwd_f32(const float* x, const float* w, const float* b, float
 /* ---- mutual-information log (transformer_vae.py:59-61, math_utils.py:51-58) ---------------------------
  * out[0] = kl[0] - marginal_kl(q), q = N(mu, exp(logvar)) from stats [B][2Z] (mu | logvar), with S posterior
  * samples per sequence: eps f32 [S][B][Z] or NULL (counter-based normals from seed). ws: f32 workspace of
- * >= 2 * S * B floats. Log-only diagnostic (not in the loss). */
+ * >= 2 * S * B floats (on return ws[s*B + i] = the marginal log density of sample s of sequence i, ws[S*B + s*B + i]
+ * = the sample's sum of squares). Z <= 4096 (SVAE_EINVAL beyond). Log-only diagnostic (not in the loss). */
 int svae_mutual_info(const float* stats, const float* eps, uint64_t seed, const float* kl, int32_t B, int32_t Z,
                      int32_t S, float* ws, float* out, svae_stream_t stream);
 
 /* ---- evaluation: log p(x|z) per sequence (continuous_autoencoder.py:82-88) ---------------------------
  * From the SVAE_EPI_CE_STATS partials of the head GEMM (which may run with C = NULL: no logits stored):
  * out[s] = sum over the rows r of sequence s (rows s*seq .. s*seq+seq-1) with labels[r] != 0 of
- * (label_logit[r] - logsumexp_r); labels 0 add 0 (the reference zeroes log_softmax column 0). */
+ * (label_logit[r] - logsumexp_r); labels 0 add 0 (the reference zeroes log_softmax column 0). part: f32
+ * [rows][ntile][2] = (max, sum exp(x - max)) per 128-column tile, (-inf, 0) for a tile without a finite entry.
+ * rows % seq == 0 (SVAE_EINVAL otherwise); out has rows / seq entries. */
 int svae_ce_seq_logprob(const float* part, int32_t ntile, const float* label_logit, const int32_t* labels,
                         int32_t rows, int32_t seq, float* out, svae_stream_t stream);
 
