@@ -649,6 +649,60 @@ int svae_latent_colstats(const float* loc, const float* scale, int32_t N, int32_
 int svae_latent_draw(const float* loc, const float* scale, const float* eps, uint64_t seed, int32_t N, int32_t Z,
                      float* z, svae_stream_t stream);
 
+/* ---- k-means of the latent index: k-means++ seeding and Lloyd's iteration over the posterior means (csrc/kmeans.hip;
+ * what stands in for the LDA topic colouring of tsne.py:38-63) ------------------------------------------------------
+ * x is f32 [N][Z], cent f32 [K][Z], both 16-byte aligned; Z a multiple of 4 in 4..256; 1 <= K <= SVAE_KMEANS_MAX_K,
+ * K <= N <= 2^24. Every entry point returns 1 before any launch on a NULL operand, a shape out of range or a
+ * workspace that is too small; the *_ws_bytes companions return 0 on a bad shape. ws: caller-owned, 8-byte aligned,
+ * contents need not survive. Nothing below uses an atomic: grids and summation orders depend on (N, K, Z) alone, so
+ * two calls on one input agree bit for bit.
+ * The distance d2(x, c) = sum_z (x_z - c_z)^2 is formed from direct differences in f32: per float4 chunk d = x - c,
+ *   then two fmaf chains (elements 0, 2 and elements 1, 3 of the chunks, in chunk order) and their sum. The order
+ *   depends on Z alone, contraction is off, and assign and seed share the function: a (row, centroid) pair has one
+ *   f32 distance, whichever kernel, lane or workgroup computes it. |error| <= (Z / 2 + 3) 2^-24 d2 to first order.
+ * svae_kmeans_assign: label int32 [N], in/out: the previous labels on entry (any value outside 0..K-1 means none), the
+ *   nearest centroid on return. Smallest distance wins, ties go to the lower centroid index, a NaN distance loses to
+ *   every number; a row whose distances are all NaN gets label 0 and d2 NaN. d2 f32 [N] or NULL: the winning distance.
+ *   changed int32 [1]: the number of rows whose label differs from its value on entry. inertia f64 [1]: sum of the
+ *   winning distances, added in f64 in a fixed order. A workgroup owns svae_kmeans_geometry's rows per workgroup (a
+ *   lane holds its rows in registers) and streams the centroids through LDS in tiles of SVAE_KMEANS_TILE_CENTROIDS;
+ *   a lane carries its best (d2, index) across the tiles. ws >= svae_kmeans_assign_ws_bytes = row blocks * 16 bytes.
+ * svae_kmeans_update: count int32 [K] = the rows per label; cent in/out: cent[c] = (float)(S_c / count_c) with S_c
+ *   the f64 sum of the rows labelled c and the division in f64; an empty cluster keeps the centroid it had on entry.
+ *   Labels outside 0..K-1 are ignored (clamped before anything is indexed). S_c is a fixed tree: the rows are cut into
+ *   B sort blocks of consecutive rows and the blocks into G groups of consecutive blocks (both from (N, K) alone:
+ *   svae_kmeans_geometry); a group's rows of cluster c are added in ascending row order, the groups in ascending order.
+ *   The route is a stable counting sort of the row numbers by label (per-block histograms, a scan over [block][K], a
+ *   scatter by rank within the block), then one segment sum per (centroid, group). ws >= svae_kmeans_update_ws_bytes
+ *   = G * K * Z * 8 (the group sums) + (B * K + K + 1 + N) * 4 (histograms, offsets, the sorted rows) rounded up to
+ *   8; B <= SVAE_KMEANS_SORT_BLOCKS and G = min(B, max(1, 4096 / K)) regrouped evenly, so at N = 2^24, K = 1024,
+ *   Z = 64 that is 2 MiB + 1 MiB + 64 MiB (the sorted row numbers).
+ * svae_kmeans_seed: k-means++. u f32 [K] or NULL: the uniforms in [0, 1), injected or drawn from the library's counter
+ *   RNG keyed by (seed, step). Step 0 takes row min(floor(u_0 N), N - 1). Step s >= 1 lowers every row's running
+ *   minimum d2 against the centroid of step s - 1, takes the inclusive prefix sums of the minima in f64 in row order
+ *   and chooses the first row i with cumsum_i > (double)u_s * total, so a row at distance 0 is never drawn; total == 0
+ *   chooses row 0. The prefix is nested three deep, each level in ascending order: over the rows of a block of
+ *   SVAE_KMEANS_SEED_BLOCK_ROWS, over the blocks of a run of 256 blocks, over the runs (cumsum_i = P + (Q + w_i)); up
+ *   to N = 256 that is the plain running sum. rows int32 [K]: the chosen rows; cent [K][Z]: their copies. The chosen
+ *   row never travels to the host: the 2 K - 1 launches queue without synchronisation. Rows must be finite. ws >=
+ *   svae_kmeans_seed_ws_bytes = ceil(N / 256) * 8 + N * 4 (rounded up to 8).
+ * svae_kmeans_geometry: geom (HOST int32 [8]) = {assign rows per workgroup (512 for Z <= 64, else 256), assign row
+ *   blocks, centroid tile, sort blocks B, rows per sort block, row groups G, seed block rows, seed blocks}. */
+#define SVAE_KMEANS_MAX_K 1024
+#define SVAE_KMEANS_TILE_CENTROIDS 32
+#define SVAE_KMEANS_SORT_BLOCKS 256
+#define SVAE_KMEANS_SEED_BLOCK_ROWS 256
+int svae_kmeans_geometry(int32_t N, int32_t K, int32_t Z, int32_t* geom);
+int64_t svae_kmeans_assign_ws_bytes(int32_t N, int32_t K, int32_t Z);
+int svae_kmeans_assign(const float* x, int32_t N, const float* cent, int32_t K, int32_t Z, int32_t* label, float* d2,
+                       int32_t* changed, double* inertia, void* ws, int64_t ws_bytes, svae_stream_t stream);
+int64_t svae_kmeans_update_ws_bytes(int32_t N, int32_t K, int32_t Z);
+int svae_kmeans_update(const float* x, int32_t N, const int32_t* label, int32_t K, int32_t Z, float* cent,
+                       int32_t* count, void* ws, int64_t ws_bytes, svae_stream_t stream);
+int64_t svae_kmeans_seed_ws_bytes(int32_t N, int32_t K, int32_t Z);
+int svae_kmeans_seed(const float* x, int32_t N, int32_t K, int32_t Z, const float* u, uint64_t seed, int32_t* rows,
+                     float* cent, void* ws, int64_t ws_bytes, svae_stream_t stream);
+
 /* library identification: returns a static string (build id, target arch). */
 const char* svae_version(void);
 

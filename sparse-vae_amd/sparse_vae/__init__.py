@@ -6,6 +6,7 @@ from .core import analytic_gaussian_rbf_mmd_sq, custom_gaussian_rbf_mmd_sq, gaus
 from .transformer_vae import TransformerVAE, TransformerVAEHparams  # noqa: F401
 from .latent_index import LatentIndex, gather_latents  # noqa: F401
 from .tsne import TSNE  # noqa: F401
+from .kmeans import KMeans  # noqa: F401
 from .batch_generation import batch_generate_samples, trim_samples  # noqa: F401
 from .text_data_module import TextDataModule  # noqa: F401
 from .trainer import Trainer, seed_everything  # noqa: F401

@@ -26,6 +26,8 @@ TSNE_ROWS_PER_BLOCK, TSNE_TILE_COLS = 512, 256       # SVAE_TSNE_ROWS_PER_BLOCK,
 PAIR_RBF, PAIR_IMQ = range(2)                        # SVAE_PAIR_RBF, SVAE_PAIR_IMQ
 PAIR_KINDS = {'rbf': PAIR_RBF, 'imq': PAIR_IMQ}
 PAIRSUM_TILE_COLS, PAIRSUM_MAX_P, MMD_REDUCE_BLOCKS = 32, 8, 256   # SVAE_PAIRSUM_TILE_COLS, _MAX_P, SVAE_MMD_REDUCE_BLOCKS
+# SVAE_KMEANS_MAX_K, _TILE_CENTROIDS, _SORT_BLOCKS, _SEED_BLOCK_ROWS
+KMEANS_MAX_K, KMEANS_TILE_CENTROIDS, KMEANS_SORT_BLOCKS, KMEANS_SEED_BLOCK_ROWS = 1024, 32, 256, 256
 
 
 class GemmDesc(ctypes.Structure):
@@ -216,6 +218,16 @@ _SIGS = {
     'svae_latent_colstats': [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                              c_void_p],
     'svae_latent_draw': [c_void_p, c_void_p, c_void_p, c_uint64, c_int32, c_int32, c_void_p, c_void_p],
+    'svae_kmeans_geometry': [c_int32, c_int32, c_int32, c_void_p],
+    'svae_kmeans_assign_ws_bytes': [c_int32, c_int32, c_int32],
+    'svae_kmeans_assign': [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_int64, c_void_p],
+    'svae_kmeans_update_ws_bytes': [c_int32, c_int32, c_int32],
+    'svae_kmeans_update': [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
+                           c_void_p],
+    'svae_kmeans_seed_ws_bytes': [c_int32, c_int32, c_int32],
+    'svae_kmeans_seed': [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
+                         c_int64, c_void_p],
     'svae_version': [],
 }
 
@@ -234,6 +246,8 @@ def _load():
                       'svae_tsne_repulse_slice_cols': c_int64, 'svae_tsne_repulse_ws_bytes': c_int64,
                       'svae_pairsum_ws_bytes': c_int64, 'svae_mmd_rowterm_ws_bytes': c_int64,
                       'svae_latent_colstats_ws_bytes': c_int64,
+                      'svae_kmeans_assign_ws_bytes': c_int64, 'svae_kmeans_update_ws_bytes': c_int64,
+                      'svae_kmeans_seed_ws_bytes': c_int64,
                       'svae_gemm_group_table_bytes': c_int64}.get(name, ctypes.c_int)
     return lib
 

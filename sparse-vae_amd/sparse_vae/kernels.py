@@ -1111,3 +1111,94 @@ def latent_draw(loc, scale, seed=0, eps=None, out=None):
     check(lib.svae_latent_draw(loc.data_ptr(), scale.data_ptr(), ptr(eps), int(seed) & (2 ** 64 - 1), n, Z,
                                out.data_ptr(), stream()), 'svae_latent_draw')
     return out
+
+
+def _kmeans_shape(x, K, name):
+    n, Z = _mmd_rows(x, f'{name} x')
+    if not 1 <= K <= min(N.KMEANS_MAX_K, n):
+        raise ValueError(f'{name}: 1 <= K <= min({N.KMEANS_MAX_K}, {n} rows), got {K}')
+    return n, Z
+
+
+def _kmeans_vec(t, dtype, numel, name):
+    _dev(t)
+    assert t.dtype == dtype and t.is_contiguous() and t.numel() == numel, name
+    return t
+
+
+def _kmeans_ws(nbytes, dev):
+    return torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+
+
+def kmeans_geometry(n, K, Z):
+    """svae_kmeans_geometry: (assign rows per workgroup, assign row blocks, centroid tile, sort blocks, rows per sort
+    block, row groups of the segment sums, seed block rows, seed blocks)."""
+    geom = (ctypes.c_int32 * 8)()
+    check(lib.svae_kmeans_geometry(n, K, Z, ctypes.addressof(geom)), 'svae_kmeans_geometry')
+    return tuple(geom)
+
+
+def kmeans_assign(x, cent, label=None, d2=None, changed=None, inertia=None, want_d2=True):
+    """svae_kmeans_assign: x f32 [N, Z] against cent f32 [K, Z] -> (label int32 [N], d2 f32 [N] or None, changed int32
+    [1], inertia f64 [1]). label is in/out: the previous labels (default: all -1, none). Ties go to the lower centroid
+    index; a NaN distance loses to every number. The workspace is allocated per call (stream-ordered by the caching
+    allocator)."""
+    K = cent.shape[0]
+    n, Z = _kmeans_shape(x, K, 'kmeans_assign')
+    dev = x.device
+    _dev(cent)
+    assert cent.dtype == f32 and cent.is_contiguous() and tuple(cent.shape) == (K, Z)
+    label = torch.full((n,), -1, dtype=torch.int32, device=dev) if label is None else label
+    _kmeans_vec(label, torch.int32, n, 'label')
+    if d2 is None and want_d2:
+        d2 = torch.empty(n, dtype=f32, device=dev)
+    if d2 is not None:
+        _kmeans_vec(d2, f32, n, 'd2')
+    changed = torch.empty(1, dtype=torch.int32, device=dev) if changed is None else changed
+    inertia = torch.empty(1, dtype=torch.float64, device=dev) if inertia is None else inertia
+    _kmeans_vec(changed, torch.int32, 1, 'changed')
+    _kmeans_vec(inertia, torch.float64, 1, 'inertia')
+    nbytes = lib.svae_kmeans_assign_ws_bytes(n, K, Z)
+    ws = _kmeans_ws(nbytes, dev)
+    check(lib.svae_kmeans_assign(x.data_ptr(), n, cent.data_ptr(), K, Z, label.data_ptr(), ptr(d2), changed.data_ptr(),
+                                 inertia.data_ptr(), ws.data_ptr(), nbytes, stream()), 'svae_kmeans_assign')
+    return label, d2, changed, inertia
+
+
+def kmeans_update(x, label, cent, count=None):
+    """svae_kmeans_update, in place on cent f32 [K, Z]: cent[c] = the f64 mean of the rows of x labelled c, rounded to
+    f32 (a fixed summation tree, no atomics); an empty cluster keeps its centroid; labels outside 0..K-1 are ignored.
+    Returns (cent, count int32 [K])."""
+    K = cent.shape[0]
+    n, Z = _kmeans_shape(x, K, 'kmeans_update')
+    dev = x.device
+    _dev(cent)
+    assert cent.dtype == f32 and cent.is_contiguous() and tuple(cent.shape) == (K, Z)
+    _kmeans_vec(label, torch.int32, n, 'label')
+    count = torch.empty(K, dtype=torch.int32, device=dev) if count is None else count
+    _kmeans_vec(count, torch.int32, K, 'count')
+    nbytes = lib.svae_kmeans_update_ws_bytes(n, K, Z)
+    ws = _kmeans_ws(nbytes, dev)
+    check(lib.svae_kmeans_update(x.data_ptr(), n, label.data_ptr(), K, Z, cent.data_ptr(), count.data_ptr(),
+                                 ws.data_ptr(), nbytes, stream()), 'svae_kmeans_update')
+    return cent, count
+
+
+def kmeans_seed(x, K, seed=0, u=None, rows=None, cent=None):
+    """svae_kmeans_seed: k-means++ (D^2 sampling) of K rows of x f32 [N, Z] -> (rows int32 [K], cent f32 [K, Z]). u:
+    f32 [K] uniforms in [0, 1), or None (the counter RNG keyed by (seed, step)). Nothing is read back: the K steps
+    queue on the stream."""
+    K = int(K)
+    n, Z = _kmeans_shape(x, K, 'kmeans_seed')
+    dev = x.device
+    if u is not None:
+        _kmeans_vec(u, f32, K, 'u')
+    rows = torch.empty(K, dtype=torch.int32, device=dev) if rows is None else rows
+    cent = torch.empty(K, Z, dtype=f32, device=dev) if cent is None else cent
+    _kmeans_vec(rows, torch.int32, K, 'rows')
+    _kmeans_vec(cent, f32, K * Z, 'cent')
+    nbytes = lib.svae_kmeans_seed_ws_bytes(n, K, Z)
+    ws = _kmeans_ws(nbytes, dev)
+    check(lib.svae_kmeans_seed(x.data_ptr(), n, K, Z, ptr(u), int(seed) & (2 ** 64 - 1), rows.data_ptr(),
+                               cent.data_ptr(), ws.data_ptr(), nbytes, stream()), 'svae_kmeans_seed')
+    return rows, cent

@@ -233,6 +233,11 @@ class LatentIndex:
         mean, var, _ = K.latent_colstats(z, scale)
         return MU.custom_gaussian_rbf_mmd_sq(z, mean, var, standardize)
 
+    def kmeans(self, n_clusters: int, **kw):
+        """k-means of the posterior means (svae_kmeans_*): KMeans(n_clusters, **kw).fit(self), see sparse_vae.kmeans."""
+        from .kmeans import KMeans
+        return KMeans(n_clusters, **kw).fit(self)
+
     # ------------------------------------------------------------------ persistence
     def save(self, path):
         """One .npz: loc, scale, titles. The derived rows are not stored (load recomputes them)."""

@@ -1,8 +1,10 @@
 """python tsne.py latents.npz --out tsne.npz [--perplexity P] [--n-iter T] [--max-points M] [--plot tsne.png] [--seed S]
+       [--clusters clusters.npz]
 
 A two-dimensional t-SNE of the posterior means gathered by gather_latents.py, the reference's tsne.py:16-36 without
-its LDA colouring. The neighbour graph, the affinities and every iteration run in libsvae's kernels
-(sparse_vae.TSNE): a GPU is required. The repulsion is the exact all-pairs sum, so an iteration costs N^2 pair
+its LDA colouring; --clusters takes the k-means labels of cluster_latents.py in its place (the output gains `labels`
+for the embedded rows and --plot colours by them). The neighbour graph, the affinities and every iteration run in
+libsvae's kernels (sparse_vae.TSNE): a GPU is required. The repulsion is the exact all-pairs sum, so an iteration costs N^2 pair
 evaluations; --max-points embeds a seeded random subset of a larger index. The output .npz holds `embedding`
 [M, 2], the subset's `rows` in the index and their `titles`. --plot scatters a random 1,000 of the points
 (matplotlib).
@@ -24,6 +26,8 @@ def build_parser():
     ap.add_argument('--metric', default='l2', choices=('l2', 'kl'))
     ap.add_argument('--plot', default=None, help='also write a scatter plot of 1,000 random points to this image')
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--clusters', default=None, help='clusters .npz written by cluster_latents.py: the output gains '
+                                                     '`labels` for the embedded rows and --plot colours by them')
     ap.add_argument('--device', default='cuda', help='torch device of the index')
     return ap
 
@@ -44,6 +48,12 @@ def main(argv=None):
     n = len(index)
     if n < 3:
         raise SystemExit(f'{args.index} holds {n} posteriors; t-SNE needs at least three')
+    labels = None
+    if args.clusters:
+        with np.load(args.clusters, allow_pickle=False) as z:
+            labels = z['labels']
+        if labels.shape != (n,):
+            raise SystemExit(f'{args.clusters} holds labels of shape {labels.shape}; {args.index} has {n} rows')
     rng = np.random.default_rng(args.seed)
     if args.max_points is not None and args.max_points < n:
         if args.max_points < 3:
@@ -57,14 +67,18 @@ def main(argv=None):
         rows = np.arange(n)
     tsne = TSNE(perplexity=args.perplexity, n_iter=args.n_iter, metric=args.metric, seed=args.seed)
     emb = tsne.fit_transform(index).cpu().numpy()
+    extra = {} if labels is None else {'labels': labels[rows].astype(np.int64)}
     with open(args.out, 'wb') as f:
-        np.savez(f, embedding=emb, rows=rows.astype(np.int64), titles=np.asarray(index.titles, dtype=np.str_))
+        np.savez(f, embedding=emb, rows=rows.astype(np.int64), titles=np.asarray(index.titles, dtype=np.str_), **extra)
     print(f'{len(rows)} of {n} rows embedded -> {args.out}')
     if args.plot:
         import matplotlib.pyplot as plt
         shown = rng.choice(len(rows), size=min(1000, len(rows)), replace=False)
         plt.figure(figsize=(8, 8))
-        plt.scatter(emb[shown, 0], emb[shown, 1], s=4)
+        if labels is None:
+            plt.scatter(emb[shown, 0], emb[shown, 1], s=4)
+        else:
+            plt.scatter(emb[shown, 0], emb[shown, 1], s=4, c=labels[rows][shown], cmap='tab20')
         plt.savefig(args.plot, dpi=150)
         print(f'{len(shown)} points plotted -> {args.plot}')
     return 0
