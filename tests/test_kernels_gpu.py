@@ -494,9 +494,11 @@ def test_zproj_fwd_multi(n, B, d, Z):
         assert torch.allclose(outs[i], ref, rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize('rows,L,D', [(64 * 512, 512, 512), (3 * 40, 40, 768), (7 * 16, 16, 256)])
+@pytest.mark.parametrize('rows,L,D', [(64 * 512, 512, 512), (3 * 40, 40, 768), (7 * 16, 16, 256), (8200, 40, 768)])
 def test_layernorm_fwd_zsplice(rows, L, D):
     # the layer's first LayerNorm with the z splice equals writing the z rows into x, then the plain LayerNorm
+    # (itself held to float64 by test_ln_kernels_gpu.py); 8200 x 768: waves 0 .. 7 take a second row, and L = 40 does
+    # not divide the wave stride of 8192: wave 0 takes the spliced row 0 and then row 8192 of x itself
     torch.manual_seed(rows + D)
     x = torch.randn(rows, D, device=dev) * 2 + 0.3
     zr = torch.randn(rows // L, D, device=dev)
