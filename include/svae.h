@@ -703,6 +703,33 @@ int64_t svae_kmeans_seed_ws_bytes(int32_t N, int32_t K, int32_t Z);
 int svae_kmeans_seed(const float* x, int32_t N, int32_t K, int32_t Z, const float* u, uint64_t seed, int32_t* rows,
                      float* cent, void* ws, int64_t ws_bytes, svae_stream_t stream);
 
+/* ---- reconstruction scoring over token ids: the integer counts behind BLEU, token accuracy and the edit rate of P
+ * (candidate, reference) pairs (csrc/textscore.hip; what stands in for reconstruction_bleu of math_utils.py:9-38, whose
+ * keys past its second order are not n-grams) --------------------------------------------------------------------------
+ * cand is int16 [P][wc], ref int16 [P][wr], row-major with the width as leading dimension, 2-byte aligned; ids are
+ * 0..32767 (taken modulo 2^15; the Python layer refuses others), and 0 is an ordinary token. cand_len, ref_len: int32
+ * [P] on the device; row p is valid in [0, len_p) with len_p clamped into [0, width], and nothing at or beyond it is
+ * read. 1 <= wc, wr <= SVAE_TEXT_MAX_LEN, P >= 1. Both entry points return 1 before any launch on a NULL operand,
+ * P < 1 or a width out of range. No atomics, no workspace: a pair's result is a pure function of its two valid parts.
+ * svae_ngram_overlap: out int32 [P][5] = {m1, m2, m3, m4, exact}. m_n = sum over the distinct n-grams g (n consecutive
+ *   tokens) of min(count_cand(g), count_ref(g)), 0 when either side has fewer than n tokens; exact = the number of
+ *   positions j < min(Lc, Lr) with cand[j] == ref[j]. One 256-thread workgroup per pair: position j gives the 64-bit
+ *   key of (token + 1) at j..j+3 (first token in the top 16 bits, 0 past the end), both sides' keys are sorted once
+ *   in LDS (bitonic over the next power of two of the longer side), order n is the keys' top n fields, and the first
+ *   key of a run of equal prefixes on the candidate side looks its run up on the reference side by binary search.
+ *   Static LDS at SVAE_TEXT_MAX_LEN = 2048: keys 2 * 2048 * 8 + tokens 2 * 2052 * 2 + partials 80 = 41,056 bytes; the
+ *   next power of two would need 81,968, past the 64 KiB of a static declaration.
+ * svae_edit_distance: out int32 [P] = the Levenshtein distance of the two valid parts with unit insert, delete and
+ *   substitute costs; an empty side gives the other side's length. One wave per pair, four pairs per workgroup:
+ *   lane l owns R >= ceil(Lc / 64) consecutive rows of the table (R the smallest of 1, 2, 3, 4, 6, 8, 12, 16, 24, 32
+ *   that covers the pair), their previous column in registers, and runs one column behind lane l - 1 (one shuffle per
+ *   step, no barrier); the reference row sits in LDS (4 * 2048 * 2 = 16 KiB). */
+#define SVAE_TEXT_MAX_LEN 2048
+int svae_ngram_overlap(const int16_t* cand, int32_t wc, const int16_t* ref, int32_t wr, const int32_t* cand_len,
+                       const int32_t* ref_len, int32_t P, int32_t* out, svae_stream_t stream);
+int svae_edit_distance(const int16_t* cand, int32_t wc, const int16_t* ref, int32_t wr, const int32_t* cand_len,
+                       const int32_t* ref_len, int32_t P, int32_t* out, svae_stream_t stream);
+
 /* library identification: returns a static string (build id, target arch). */
 const char* svae_version(void);
 

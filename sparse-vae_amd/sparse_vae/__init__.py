@@ -7,6 +7,8 @@ from .transformer_vae import TransformerVAE, TransformerVAEHparams  # noqa: F401
 from .latent_index import LatentIndex, gather_latents  # noqa: F401
 from .tsne import TSNE  # noqa: F401
 from .kmeans import KMeans  # noqa: F401
+from .reconstruction import (ReconstructionScores, interpolate_latents, reference_rows,  # noqa: F401
+                             score_reconstructions)
 from .batch_generation import batch_generate_samples, trim_samples  # noqa: F401
 from .text_data_module import TextDataModule  # noqa: F401
 from .trainer import Trainer, seed_everything  # noqa: F401

@@ -28,6 +28,7 @@ PAIR_KINDS = {'rbf': PAIR_RBF, 'imq': PAIR_IMQ}
 PAIRSUM_TILE_COLS, PAIRSUM_MAX_P, MMD_REDUCE_BLOCKS = 32, 8, 256   # SVAE_PAIRSUM_TILE_COLS, _MAX_P, SVAE_MMD_REDUCE_BLOCKS
 # SVAE_KMEANS_MAX_K, _TILE_CENTROIDS, _SORT_BLOCKS, _SEED_BLOCK_ROWS
 KMEANS_MAX_K, KMEANS_TILE_CENTROIDS, KMEANS_SORT_BLOCKS, KMEANS_SEED_BLOCK_ROWS = 1024, 32, 256, 256
+TEXT_MAX_LEN = 2048                                  # SVAE_TEXT_MAX_LEN
 
 
 class GemmDesc(ctypes.Structure):
@@ -228,6 +229,8 @@ _SIGS = {
     'svae_kmeans_seed_ws_bytes': [c_int32, c_int32, c_int32],
     'svae_kmeans_seed': [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
                          c_int64, c_void_p],
+    'svae_ngram_overlap': [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p],
+    'svae_edit_distance': [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p],
     'svae_version': [],
 }
 

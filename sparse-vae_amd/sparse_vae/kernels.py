@@ -1202,3 +1202,45 @@ def kmeans_seed(x, K, seed=0, u=None, rows=None, cent=None):
     check(lib.svae_kmeans_seed(x.data_ptr(), n, K, Z, ptr(u), int(seed) & (2 ** 64 - 1), rows.data_ptr(),
                                cent.data_ptr(), ws.data_ptr(), nbytes, stream()), 'svae_kmeans_seed')
     return rows, cent
+
+
+def _text_pairs(cand, ref, cand_len, ref_len, name):
+    _dev(cand, ref, cand_len, ref_len)
+    for t, what in ((cand, 'candidates'), (ref, 'references')):
+        if t.dim() != 2 or t.dtype != torch.int16 or not t.is_contiguous():
+            raise ValueError(f'{name}: {what} must be contiguous int16 [P, W], got {t.dtype} {tuple(t.shape)}')
+        if not 1 <= t.shape[1] <= N.TEXT_MAX_LEN:
+            raise ValueError(f'{name}: {what} are {t.shape[1]} wide; the kernels take 1..{N.TEXT_MAX_LEN} '
+                             f'(SVAE_TEXT_MAX_LEN)')
+    P = cand.shape[0]
+    if P < 1 or ref.shape[0] != P:
+        raise ValueError(f'{name}: {P} candidates against {ref.shape[0]} references')
+    for t in (cand_len, ref_len):
+        if t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != (P,):
+            raise ValueError(f'{name}: lengths must be contiguous int32 [{P}], got {t.dtype} {tuple(t.shape)}')
+    return P
+
+
+def ngram_overlap(cand, ref, cand_len, ref_len, out=None):
+    """svae_ngram_overlap: cand int16 [P, wc], ref int16 [P, wr], lengths int32 [P] (clamped into [0, width] by the
+    kernel) -> int32 [P, 5] = (m1, m2, m3, m4, exact): the clipped n-gram match counts of orders 1..4 and the number of
+    equal positions. Ids must be 0..32767 (not checked here: that would synchronise)."""
+    P = _text_pairs(cand, ref, cand_len, ref_len, 'ngram_overlap')
+    out = torch.empty(P, 5, dtype=torch.int32, device=cand.device) if out is None else out
+    _dev(out)
+    assert out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (P, 5)
+    check(lib.svae_ngram_overlap(cand.data_ptr(), cand.shape[1], ref.data_ptr(), ref.shape[1], cand_len.data_ptr(),
+                                 ref_len.data_ptr(), P, out.data_ptr(), stream()), 'svae_ngram_overlap')
+    return out
+
+
+def edit_distance(cand, ref, cand_len, ref_len, out=None):
+    """svae_edit_distance: the token Levenshtein distance (unit costs) of every pair -> int32 [P]. Operands as
+    ngram_overlap."""
+    P = _text_pairs(cand, ref, cand_len, ref_len, 'edit_distance')
+    out = torch.empty(P, dtype=torch.int32, device=cand.device) if out is None else out
+    _dev(out)
+    assert out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (P,)
+    check(lib.svae_edit_distance(cand.data_ptr(), cand.shape[1], ref.data_ptr(), ref.shape[1], cand_len.data_ptr(),
+                                 ref_len.data_ptr(), P, out.data_ptr(), stream()), 'svae_edit_distance')
+    return out

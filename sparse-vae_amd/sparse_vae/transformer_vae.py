@@ -531,3 +531,27 @@ class TransformerVAE(ContinuousVAEHooks, LanguageModel):
         stats = eng.posterior(ids, pad if pad is not None else False)
         return Normal(stats[:, :Z].reshape(-1, 1, Z).clone(), stats[:, Z:].exp().sqrt().reshape(-1, 1, Z),
                       validate_args=False)
+
+    @torch.no_grad()
+    def autoencode(self, batch, max_length: Optional[int] = None, sample_posterior: bool = False,
+                   slots: Optional[int] = None, seed: int = 0, **gen):
+        """Reconstruct a batch through its latent (reconstruct.py:31-32 at corpus scale): q(z|x) from `encode`, z its
+        mean (or, with sample_posterior, one draw through svae_latent_draw keyed by `seed`), then
+        `sample_stream(max_length, B, z=z, **gen)`. Returns (ids int16 [B, max_length - 1] on the device, zero after
+        each row's end, and the posterior). max_length defaults to the batch's width + 1; gen takes GenerationState's
+        settings, with temperature 0.7 (reconstruct.py:32) unless given. Raises below kl_weight 1, where the model
+        does not sample."""
+        if self.hparams.kl_weight < 1.0:
+            raise RuntimeError(f'autoencode: the model does not sample below kl_weight 1 (it is '
+                               f'{self.hparams.kl_weight})')
+        posterior = self.encode(batch)
+        B, _, Z = posterior.loc.shape
+        if max_length is None:
+            ids = batch['token_ids']
+            max_length = (ids.as_raw() if isinstance(ids, PaddedTensor) else ids).shape[-1] + 1
+        z = posterior.loc
+        if sample_posterior:
+            z = K.latent_draw(posterior.loc.reshape(B, Z).contiguous(), posterior.scale.reshape(B, Z).contiguous(),
+                              seed=seed).view(B, 1, Z)
+        gen.setdefault('temperature', 0.7)
+        return self.sample_stream(int(max_length), B, slots=slots, z=z, **gen), posterior
