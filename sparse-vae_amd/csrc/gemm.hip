@@ -1051,6 +1051,7 @@ __device__ __forceinline__ void g3_reg_epilogue_ld(const GP& p, const f32x4 (&ac
     return;
   } else if constexpr (EPI == SVAE_EPI_GELU_BWD) {
     const int cs = ((g & 1) ? 16 : 0) + ((g & 2) ? 8 : 0);   // column of this lane's 8 within a 32-column pair
+    const bool tail = __builtin_amdgcn_readfirstlane((int)((p.N & 7) && nb < p.N && nb + 64 > p.N));   // wave-uniform
     auto ld_row = [&](int i, u32x4 (&r)[2]) {
       const int m = m0 + wr * 128 + i * 16 + li;
 #pragma unroll
@@ -1058,6 +1059,12 @@ __device__ __forceinline__ void g3_reg_epilogue_ld(const GP& p, const f32x4 (&ac
         const int n = nb + 32 * jp + cs;
         r[jp] = (m < p.M && n + 8 <= p.N) ? *(const u32x4*)((const bf16*)p.aux + (long long)m * p.ldaux + n)
                                           : (u32x4){0u, 0u, 0u, 0u};
+        // N % 8 == 4: the row's last group holds 4 valid columns, which store_rows_w16 stores (only the wave whose 64
+        // columns cross N takes the branch)
+        if (tail && m < p.M && n < p.N && n + 8 > p.N) {
+          const u32x2 h = *(const u32x2*)((const bf16*)p.aux + (long long)m * p.ldaux + n);
+          r[jp] = (u32x4){h[0], h[1], 0u, 0u};
+        }
       }
     };
     u32x4 cur[2], nxt[2];

@@ -1,5 +1,5 @@
 """Sentinel-filled output buffers for the one-kernel-at-a-time GPU tests (test_head_kernels_gpu.py,
-test_attn_kernels_gpu.py, test_ln_kernels_gpu.py): a kernel's output is a view into a larger buffer whose remainder holds SENTINEL, and
+test_attn_kernels_gpu.py, test_ln_kernels_gpu.py, test_gemm_kernels_gpu.py): a kernel's output is a view into a larger buffer whose remainder holds SENTINEL, and
 intact() checks after the launch that nothing outside the view was written. report() / ratio() print each measured
 figure beside its bound before asserting it."""
 import torch

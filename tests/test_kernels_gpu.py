@@ -149,6 +149,7 @@ def test_linear_dw_pair_exact(shapes):
 
 @pytest.mark.parametrize('M,Nn,Kk', [(300, 256, 192), (4000, 3072, 520)])   # small: 128-tile kernels; big: gemm256
 def test_gemm_epilogues(M, Nn, Kk):
+    # (per element, per kernel and against the numpy dropout mask: test_gemm_kernels_gpu.py::test_epilogues_per_element)
     torch.manual_seed(0)
     X = torch.randn(M, Kk, device=dev).bfloat16()
     W = (torch.randn(Nn, Kk, device=dev) * 0.1).bfloat16()
@@ -223,6 +224,7 @@ def test_gemm_dropout_resid_bf16_copy(M, Nn, Kk):
 @pytest.mark.parametrize('M,Nn,Kk', [(64, 512, 2048), (37, 520, 72), (1, 2048, 512), (64, 512, 64)])
 def test_gemm_skinny_epilogues(M, Nn, Kk):
     # M <= 64: the K-split skinny kernel (one row per sequence: encoder bottleneck, q(z|x), z projections)
+    # (per element at the k-step and wave edges: test_gemm_kernels_gpu.py::test_epilogues_per_element[skinny-*])
     torch.manual_seed(M + Nn + Kk)
     Ai = torch.randint(-2, 3, (M, Kk), device=dev).float()
     Bi = torch.randint(-2, 3, (Nn, Kk), device=dev).float()
@@ -263,7 +265,8 @@ def test_gemm_skinny_epilogues(M, Nn, Kk):
 
 @pytest.mark.parametrize('M,Nn,Kk', [(8200, 2056, 520), (8192, 2048, 512)])
 def test_gemm_many_tiles_epilogues(M, Nn, Kk):
-    # >= 512 tiles of 256 x 128: the shapes gemm_ov takes when enabled (SVAE_GEMM_OV=1; ragged M, N, K in the first)
+    # 297 and 256 tiles on gemm256, the first persistent (blocks take a second tile; ragged M, N, K there)
+    # (test_gemm_kernels_gpu.py holds the same epilogues per element, also at N % 8 == 4 and 260 / 231 tiles)
     torch.manual_seed(M + Kk)
     Ai = torch.randint(-2, 3, (M, Kk), device=dev).float()
     Bi = torch.randint(-2, 3, (Nn, Kk), device=dev).float()
@@ -301,6 +304,7 @@ def test_gemm_many_tiles_epilogues(M, Nn, Kk):
 
 @pytest.mark.parametrize('B,L,d', [(2, 96, 256), (16, 512, 512), (24, 512, 512)])
 def test_gemm_rotary_matches_reference_rotation(B, L, d):
+    # (per element, rot_d no power of two, rot_seq 40 / 5: test_gemm_kernels_gpu.py::test_rotary_per_element)
     torch.manual_seed(1)
     X = torch.randn(B * L, d, device=dev).bfloat16()
     W = (torch.randn(3 * d, d, device=dev) * 0.05).bfloat16()
@@ -1069,7 +1073,8 @@ def test_resid_ln_fwd(D, p, with_x, with_z, with_ln, ydt):
                                             (64, 128, 128, 16, 1)])         # skinny GEMM, hd 16
 def test_gemm_delta_epilogue(M, Nn, Kk, hd, seq):
     """svae_gemm's delta (the attention backward's rowsum(dO . O) per head, written by the dO GEMM): C identical to
-    the plain BF16 GEMM, delta against torch on the bf16 C and the f32 O copy (summation order differs: 1e-5)."""
+    the plain BF16 GEMM, delta against torch on the bf16 C and the f32 O copy (summation order differs: 1e-5).
+    (Per (row, head) in guarded buffers, ld_o32 > N: test_gemm_kernels_gpu.py::test_bf16_delta_per_row_and_head.)"""
     torch.manual_seed(M + hd)
     A = torch.randn(M, Kk, device=dev).bfloat16()
     W = (torch.randn(Nn, Kk, device=dev) * 0.05).bfloat16()
