@@ -533,6 +533,57 @@ int svae_slot_refill(int32_t* pos, int32_t* key, int64_t* ids, int32_t T, int32_
                      const float* z_all, float* z_slot, int32_t Z, int32_t num_samples, int32_t* next,
                      int32_t* completed, svae_stream_t stream);
 
+/* ---- beam search decoding. R = B * W decoder rows, row r = b * W + w is hypothesis w of document b;
+ * 1 <= W <= 16 (SVAE_BEAM_MAX_W), 3 <= T <= 32768, R <= 65535. `cur` is the device int32 of the dec_* kernels: the
+ * index c of the token this step generates (1 .. T-2). All pointers are static over a decode, so one captured step
+ * graph replays. Per row: cum f32 [R] (cumulative log-probability, -inf = dead row), ids int64 [R][T] (ids[r][0] =
+ * start token), anc uint8 [R][T]: anc[r][j] = the beam of the same document whose cache row holds this hypothesis's
+ * key at position j. Per document: a pool of up to W finished hypotheses, pool_score / pool_logp f32 [B][W],
+ * pool_len int32 [B][W], pool_ids int64 [B][W][T], pool_n int32 [B]; done uint8 [B]. len_pen f32 [T]: len_pen[l] =
+ * l^alpha, computed by the caller (entry 0 unused); alpha_pos = (alpha > 0).
+ * beam_attn: svae_dec_attn over rows r with p = cur-1: appends k, v at p to row r's own cache row and reads the
+ *   visible key j < p from cache row (r / W) * W + anc[r][j]. Same visible set, body and summation order as
+ *   dec_attn: with anc[r][j] = r % W the outputs are equal bit for bit.
+ * beam_topk: per row with cum[r] > -inf whose document is not done (done may be NULL): lse = max + logf(sum
+ *   expf(x - max)), the C = 2W largest logits by (value descending, id ascending), cand_score[r][k] = cum[r] +
+ *   ((x - max) - logf(sum)), cand_tok[r][k] = id. Other rows' outputs are not written. 2W <= V <= 32768; R need not
+ *   be a multiple of W here (done then has ceil(R / W) entries).
+ * beam_select: per document not done, at c = *cur in 1 .. T-2 (nothing is written otherwise): the W * C candidates of
+ *   its live rows ordered by (score descending, beam ascending, then the row's own candidate order, which beam_topk
+ *   emits by logit descending, token ascending: for equal scores of one beam that is token ascending, and it stays
+ *   the order of the exact sums where cum + logp rounds two candidates together), the best C walked in that order:
+ *   an end_token candidate of rank < W enters the pool with score s / len_pen[c], length c (a free slot, else it
+ *   replaces the worst entry -- lowest score, the later slot among equals -- if strictly better); one of rank >= W is
+ *   dropped; any other becomes the next live hypothesis, in order, until W are live. Writes cum (-inf for rows left
+ *   without a hypothesis), for each new row ids = parent's ids[0..c-1] + token and anc = parent's anc[0..c-2] +
+ *   parent at c-1, the pool rows that arrived (prefix, end token, zeros), done[b] = pool full and
+ *   best live cum / len_pen[alpha_pos ? T-2 : c] <= worst pool score, stamp[b] = c, and, when the three history
+ *   pointers are given (int32, int32, f32 [T][R]), parent / token / score of each new row at [c][r] (-1, -1, -inf
+ *   for a row left dead). The new id and ancestry rows are written to ids_next / anc_next (a row's parent may be
+ *   another row of the document) and copied back by a second launch, which also writes *not_done = the number of
+ *   documents with done == 0. No atomics.
+ * beam_finalize: per document: if not done, its live rows (cum > -inf, in beam order) enter the pool as unfinished
+ *   with score cum / len_pen[T-2] and length T-2 under the same rule; the pool is sorted by score descending
+ *   (stable in slot order) and the best n <= W written: out_ids int64 [B][n][T-1] (start token excluded, zero from
+ *   the entry's length on), out_scores, out_logp f32 [B][n], out_len int32 [B][n]. Missing entries: -inf, 0. The
+ *   pool and the rows themselves are not modified. */
+#define SVAE_BEAM_MAX_W 16
+int svae_beam_attn(const float* qkv, int64_t ldq, float* kcache, float* vcache, const uint8_t* anc, int32_t R,
+                   int32_t W, int32_t H, int32_t hd, int32_t T, const int32_t* cur, int32_t window, float scale,
+                   float* O, int64_t ldo, svae_stream_t stream);
+int svae_beam_topk(const float* logits, int64_t ldl, int32_t V, int32_t R, int32_t W, const float* cum,
+                   const uint8_t* done, float* cand_score, int32_t* cand_tok, svae_stream_t stream);
+int svae_beam_select(const float* cand_score, const int32_t* cand_tok, float* cum, int64_t* ids, uint8_t* anc,
+                     int64_t* ids_next, uint8_t* anc_next, int32_t B, int32_t W, int32_t T, const int32_t* cur,
+                     int32_t end_token, const float* len_pen, int32_t alpha_pos, float* pool_score, float* pool_logp,
+                     int32_t* pool_len, int64_t* pool_ids, int32_t* pool_n, uint8_t* done, int32_t* not_done,
+                     int32_t* stamp, int32_t* hist_parent, int32_t* hist_token, float* hist_score,
+                     svae_stream_t stream);
+int svae_beam_finalize(const float* cum, const int64_t* ids, int32_t B, int32_t W, int32_t T, const float* len_pen,
+                       const float* pool_score, const float* pool_logp, const int32_t* pool_len,
+                       const int64_t* pool_ids, const int32_t* pool_n, const uint8_t* done, int32_t n,
+                       int64_t* out_ids, float* out_scores, float* out_logp, int32_t* out_len, svae_stream_t stream);
+
 /* ---- latent index: posterior gathering and k-NN search (gather_latents.py:26-31, knn.py:28-50,
  * math_utils.py:90-101) -------------------------------------------------------------------------------
  * A corpus is N posteriors q(z|x) = N(mu, scale^2), f32 [N][Z]; Z % 4 == 0, 4 <= Z <= 256, N >= 1 (int32); mu,

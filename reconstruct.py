@@ -12,6 +12,10 @@ accuracy, the edit rate (TER), mean lengths, the number of documents and how man
     matches, totals int32 [N, 4], exact, edit, ref_len int32 [N]: the integer counts every figure above is made of,
     titles   where the batches carry them,
     hparams  the model's hyperparameters and the generation settings, as a JSON string.
+--beams N [--length-penalty A] decodes by beam search instead (TransformerVAE.beam_search: the most probable
+continuation under p(x|z), no seed, scores comparable between latents), in the corpus mode and under --interpolate. The
+.npz then also holds beam_scores and beam_log_probs f32 [N] (log p / length ** A, and log p); the sampling flags
+(--top-k, --top-p, --temperature, --slots) are ignored, with a note on stderr.
 Originals and reconstructions are at most SVAE_TEXT_MAX_LEN = 2048 tokens, so --max-length is at most 2049.
 
 --interpolate A B [--steps 9] [--interp-mode linear|slerp] decodes along the line between the posterior means of two
@@ -49,6 +53,8 @@ def build_parser():
     ap.add_argument('--top-p', type=float, default=0.9)
     ap.add_argument('--temperature', type=float, default=0.7)
     ap.add_argument('--repetition-penalty', type=float, default=1.2)
+    ap.add_argument('--beams', type=int, default=None, help='decode by beam search with this many beams (1..16)')
+    ap.add_argument('--length-penalty', type=float, default=1.0, help='with --beams: score = log p / length ** A')
     ap.add_argument('--start-token', type=int, default=None, help='default: the model\'s ([CLS] = 1)')
     ap.add_argument('--end-token', type=int, default=None, help='default: the model\'s ([SEP] = 2)')
     ap.add_argument('--sample-posterior', action='store_true', help='decode from a posterior draw, not the mean')
@@ -72,6 +78,7 @@ def _titles(batch):
 
 def interpolate(model, data, loader, args, gen, end):
     """Decode --steps latents between the posterior means of documents A and B; returns the ids [steps, T - 1]."""
+    import torch
     from sparse_vae import interpolate_latents, trim_samples
     want, found, row0 = list(args.interpolate), {}, 0
     for batch in loader:
@@ -91,12 +98,17 @@ def interpolate(model, data, loader, args, gen, end):
         raise SystemExit(f'no document named {missing} in the {row0} documents read (titles, or row numbers where the '
                          f'batches have no titles)')
     z = interpolate_latents(found[want[0]], found[want[1]], args.steps, mode=args.interp_mode)
-    out = model.sample_stream(args.max_length, args.steps, slots=args.slots, z=z, **gen)
+    if args.beams is not None:
+        res = model.beam_search(args.max_length, z, num_beams=args.beams, length_penalty=args.length_penalty,
+                                repetition_penalty=args.repetition_penalty)
+        out, scores = res.ids[:, 0].to(torch.int16), res.scores[:, 0].tolist()
+    else:
+        out, scores = model.sample_stream(args.max_length, args.steps, slots=args.slots, z=z, **gen), None
     if out is None:
         raise SystemExit('the model does not sample below kl_weight 1')
     for i, row in enumerate(trim_samples(out, end)):
         text = data.tokenizer.decode(row.tolist()) if not data.synthetic else ' '.join(str(t) for t in row.tolist())
-        print(f'[{i / (args.steps - 1):.3f}] {text}')
+        print(f'[{i / (args.steps - 1):.3f}] {text}' + (f'  ({scores[i]:.4f})' if scores is not None else ''))
     return out.cpu().numpy()
 
 
@@ -124,6 +136,13 @@ def main(argv=None):
     end = model.end_token if model.end_token is not None else 2
     gen = dict(top_k=args.top_k, top_p=args.top_p, temperature=args.temperature,
                repetition_penalty=args.repetition_penalty)
+    beam = {}
+    if args.beams is not None:
+        if not 1 <= args.beams <= 16:
+            raise SystemExit(f'--beams {args.beams}: 1..16')
+        beam = dict(num_beams=args.beams, length_penalty=args.length_penalty)
+        print('--beams: beam search decoding; --top-k, --top-p, --temperature and --slots are ignored',
+              file=sys.stderr)
     data = TextDataModule(**config.get('data', {}))
     data.prepare_data()
     data.setup('predict')
@@ -137,14 +156,17 @@ def main(argv=None):
         return interpolate(model, data, loader, args, gen, end)
 
     window = T - 1
-    parts, ids_out, titles, truncated = [], [], [], 0
+    parts, ids_out, titles, truncated, beam_scores, beam_logp = [], [], [], 0, [], []
     for k, batch in enumerate(loader):
         ref, ref_len = reference_rows(batch)
         ref, ref_len = ref.to(model.device), ref_len.to(model.device)
         truncated += int((ref_len > window).sum())
         ref, ref_len = ref[:, :window], ref_len.clamp(max=window)
         ids, _ = model.autoencode(batch, max_length=T, sample_posterior=args.sample_posterior, slots=args.slots,
-                                  seed=args.seed + k, **gen)
+                                  seed=args.seed + k, **beam, **gen)
+        if beam:
+            beam_scores.append(model.last_beam_result.scores[:, 0].cpu().numpy())
+            beam_logp.append(model.last_beam_result.log_probs[:, 0].cpu().numpy())
         parts.append(score_reconstructions(ids, ref, ref_lengths=ref_len, end_token=end))
         ids_out.append(ids.cpu().numpy())
         t = _titles(batch)
@@ -156,11 +178,14 @@ def main(argv=None):
     figures = dict(scores.summary(), documents=len(scores), truncated=truncated)
     hparams = dict(model=dict(config['model']),
                    generation=dict(gen, max_length=T, slots=args.slots, end_token=end, seed=args.seed,
-                                   sample_posterior=bool(args.sample_posterior)))
+                                   sample_posterior=bool(args.sample_posterior), **beam))
     i32 = lambda a: np.asarray(a).astype(np.int32)                    # noqa: E731
     saved = dict(ids=np.concatenate(ids_out).astype(np.int16), lengths=i32(scores.cand_len),
                  matches=i32(scores.matches), totals=i32(scores.totals), exact=i32(scores.exact),
                  edit=i32(scores.edit), ref_len=i32(scores.ref_len), hparams=json.dumps(hparams, default=str))
+    if beam:
+        saved['beam_scores'] = np.concatenate(beam_scores).astype(np.float32)
+        saved['beam_log_probs'] = np.concatenate(beam_logp).astype(np.float32)
     if titles:
         saved['titles'] = np.array(titles)
     np.savez(args.out, **saved)

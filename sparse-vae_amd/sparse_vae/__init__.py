@@ -4,6 +4,7 @@ from .core import *  # noqa: F401,F403
 from .core import PaddedTensor, RAdam, marginal_kl, pairwise_gaussian_kl  # noqa: F401
 from .core import analytic_gaussian_rbf_mmd_sq, custom_gaussian_rbf_mmd_sq, gaussian_imq_mmd_sq  # noqa: F401
 from .transformer_vae import TransformerVAE, TransformerVAEHparams  # noqa: F401
+from .decoding import BeamDecoder, BeamResult  # noqa: F401
 from .latent_index import LatentIndex, gather_latents  # noqa: F401
 from .tsne import TSNE  # noqa: F401
 from .kmeans import KMeans  # noqa: F401

@@ -29,6 +29,7 @@ PAIRSUM_TILE_COLS, PAIRSUM_MAX_P, MMD_REDUCE_BLOCKS = 32, 8, 256   # SVAE_PAIRSU
 # SVAE_KMEANS_MAX_K, _TILE_CENTROIDS, _SORT_BLOCKS, _SEED_BLOCK_ROWS
 KMEANS_MAX_K, KMEANS_TILE_CENTROIDS, KMEANS_SORT_BLOCKS, KMEANS_SEED_BLOCK_ROWS = 1024, 32, 256, 256
 TEXT_MAX_LEN = 2048                                  # SVAE_TEXT_MAX_LEN
+BEAM_MAX_W = 16                                      # SVAE_BEAM_MAX_W
 
 
 class GemmDesc(ctypes.Structure):
@@ -194,6 +195,14 @@ _SIGS = {
                          c_int32, c_float, c_int32, c_float, c_uint64, c_void_p],
     'svae_slot_refill': [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32,
                          c_void_p, c_void_p, c_void_p],
+    'svae_beam_attn': [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                       c_void_p, c_int32, c_float, c_void_p, c_int64, c_void_p],
+    'svae_beam_topk': [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    'svae_beam_select': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                         c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    'svae_beam_finalize': [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     'svae_mutual_info': [c_void_p, c_void_p, c_uint64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                          c_void_p],
     'svae_latent_prepare': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p],

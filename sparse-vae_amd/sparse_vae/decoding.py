@@ -18,10 +18,14 @@ reads exactly the keys the reference's sliding-window cache keeps (attention.py:
 StreamDecoder (below) is the bulk generator: the same step with one position per row, finished rows refilled on
 the device with the next sample, for `TransformerVAE.sample_stream`.
 """
+import math
+from types import SimpleNamespace
+from typing import NamedTuple, Optional
+
 import torch
 
 from . import kernels as K
-from ._native import EPI_F32, EPI_GELU, EPI_ROTARY_BF16
+from ._native import BEAM_MAX_W, EPI_F32, EPI_GELU, EPI_ROTARY_BF16
 
 f32 = torch.float32
 
@@ -57,13 +61,26 @@ class KVDecoder:
         # q | k | v weights and biases are adjacent in the arena: one [3d, d] operand; rotary on q and k
         K.dec_linear(self.h, P.f(a + 'q_linear.weight'), self.qkv, B, 3 * d, d, bias=P.f(a + 'q_linear.bias'),
                      epi=EPI_ROTARY_BF16, rot=self.rot, rot_cols=2 * d, rot_d=d, cur=st.cur, part=self.part)
-        K.dec_attn(self.qkv, self.kc[i], self.vc[i], self.O, B, self.H, self.hd, self.T, st.cur, self.window)
+        self._attn(i)
         K.dec_linear(self.O, P.f(a + 'output_linear.weight'), self.x1, B, d, d, bias=P.f(a + 'output_linear.bias'),
                      resid=x_in, part=self.part)
         K.layernorm_fwd_f32(self.x1, P.f(pre + 'ffn_layer_norm.weight'), P.f(pre + 'ffn_layer_norm.bias'), self.h, B, d)
         K.dec_linear(self.h, P.f(pre + 'ffn.0.weight'), self.f, B, 4 * d, d, bias=P.f(pre + 'ffn.0.bias'), epi=EPI_GELU,
                      part=self.part)
         K.dec_linear(self.f, P.f(pre + 'ffn.2.weight'), x_out, B, d, 4 * d, resid=self.x1, part=self.part)
+
+    def _attn(self, i):
+        K.dec_attn(self.qkv, self.kc[i], self.vc[i], self.O, self.B, self.H, self.hd, self.T, self.st.cur, self.window)
+
+    def _choose(self):
+        """GenerationState.process_logits (generation.py:30-77) on all rows; dead rows are skipped in-kernel."""
+        B, st = self.B, self.st
+        if st.repetition_penalty > 1.0:
+            K.dec_penalty(self.logits, B, None, st.output_ids, self.T, st.cur, st.live_sample_mask,
+                          float(st.repetition_penalty))
+        K.dec_sample(self.logits, self.V, B, None, st.output_ids, self.T, st.cur, st.live_sample_mask,
+                     int(st.end_token), float(st.temperature), int(st.top_k), float(st.top_p), st.seed, st.live_count)
+        K.dec_advance(st.cur)
 
     def _step(self, first):
         P, B, d, st = self.P, self.B, self.d, self.st
@@ -82,13 +99,7 @@ class KVDecoder:
                      epi=EPI_GELU, part=self.part)
         K.layernorm_fwd_f32(self.h0, P.f('output_layer.2.weight'), P.f('output_layer.2.bias'), self.hh, B, d)
         K.dec_linear(self.hh, P.f('input_layer.0.weight'), self.logits, B, self.V, d, bias=P.f('output_layer.3.bias'))
-        # GenerationState.process_logits (generation.py:30-77) on all rows; dead rows are skipped in-kernel
-        if st.repetition_penalty > 1.0:
-            K.dec_penalty(self.logits, B, None, st.output_ids, self.T, st.cur, st.live_sample_mask,
-                          float(st.repetition_penalty))
-        K.dec_sample(self.logits, self.V, B, None, st.output_ids, self.T, st.cur, st.live_sample_mask,
-                     int(st.end_token), float(st.temperature), int(st.top_k), float(st.top_p), st.seed, st.live_count)
-        K.dec_advance(st.cur)
+        self._choose()
 
     def run(self, check_every=8):
         """The reference's `while not state.should_stop()` loop (transformer_vae.py:114-126)."""
@@ -274,6 +285,135 @@ class StreamDecoder:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self._step()
+        for t, v in zip(state, saved):
+            t.copy_(v)
+        self.graph = g
+
+
+class BeamResult(NamedTuple):
+    """TransformerVAE.beam_search's result: the best `num_return` hypotheses of each document, best first."""
+    ids: torch.Tensor            # int64 [B, n, T - 1]: start token excluded, zero after the end token
+    scores: torch.Tensor         # f32 [B, n]: log_probs / length ** length_penalty
+    log_probs: torch.Tensor      # f32 [B, n]: the un-normalised sums
+    lengths: torch.Tensor        # int32 [B, n]: generated tokens, the end token included
+    history: Optional[dict] = None   # parent, token int32 and score f32 [T, R] of every step's new rows
+
+
+class BeamState:
+    """The device state of a beam search (include/svae.h "beam search decoding"): per row the cumulative
+    log-probability, the id row and the ancestry row; per document the pool of finished hypotheses and the done
+    flag; the step index `cur`. Every buffer keeps its address over a decode."""
+
+    def __init__(self, B, W, T, start_token, end_token, alpha, device, history=False):
+        B, W, T = int(B), int(W), int(T)
+        if not 1 <= W <= BEAM_MAX_W:
+            raise ValueError(f'num_beams {W}: 1..{BEAM_MAX_W}')
+        if B < 1 or not 3 <= T <= 32768 or B * W > 65535:
+            raise ValueError(f'beam search: {B} documents x {W} beams (at most 65535 rows), max_length {T} (3..32768)')
+        self.B, self.W, self.T, self.alpha = B, W, T, float(alpha)
+        self.start_token, self.end_token = int(start_token), int(end_token)
+        R, dev = B * W, torch.device(device)
+        z = lambda dt, *s: torch.zeros(*s, device=dev, dtype=dt)   # noqa: E731
+        self.cum = torch.full((B, W), -math.inf, device=dev, dtype=f32)
+        self.cum[:, 0] = 0.0                                       # step 1 expands one hypothesis per document
+        self.ids, self.ids_next = z(torch.int64, R, T), z(torch.int64, R, T)
+        self.ids[:, 0] = self.start_token
+        self.anc, self.anc_next = z(torch.uint8, R, T), z(torch.uint8, R, T)
+        self.cur = torch.ones(1, device=dev, dtype=torch.int32)
+        # l ** alpha in float64, rounded once: the kernels and the float64 reference divide by the same numbers
+        self.len_pen = torch.arange(T, dtype=torch.float64).clamp_(min=1).pow_(self.alpha).to(f32).to(dev)
+        self.pool_score, self.pool_logp = z(f32, B, W), z(f32, B, W)
+        self.pool_len, self.pool_ids, self.pool_n = z(torch.int32, B, W), z(torch.int64, B, W, T), z(torch.int32, B)
+        self.done, self.stamp = z(torch.uint8, B), z(torch.int32, B)
+        self.not_done = torch.full((1,), B, device=dev, dtype=torch.int32)
+        self.cand_score, self.cand_tok = z(f32, R, 2 * W), z(torch.int32, R, 2 * W)
+        self.hist_parent = self.hist_token = self.hist_score = None
+        if history:
+            self.hist_parent = torch.full((T, R), -1, device=dev, dtype=torch.int32)
+            self.hist_token = torch.full((T, R), -1, device=dev, dtype=torch.int32)
+            self.hist_score = torch.full((T, R), -math.inf, device=dev, dtype=f32)
+
+    def tensors(self):
+        """Everything a step changes (what a graph capture saves and restores)."""
+        ts = [self.cum, self.ids, self.anc, self.cur, self.pool_score, self.pool_logp, self.pool_len, self.pool_ids,
+              self.pool_n, self.done, self.stamp, self.not_done]
+        return ts + [t for t in (self.hist_parent, self.hist_token, self.hist_score) if t is not None]
+
+    def history(self):
+        if self.hist_parent is None:
+            return None
+        return dict(parent=self.hist_parent, token=self.hist_token, score=self.hist_score)
+
+
+class BeamDecoder(KVDecoder):
+    """Beam search over p(x|z): KVDecoder's step on R = B * W rows (row b * W + w is hypothesis w of document b; z
+    repeated per beam), with beam_attn for dec_attn and beam_topk -> beam_select -> dec_advance for dec_sample. The
+    hypotheses are reordered every step, the KV caches never: attention finds a hypothesis's key j in the cache row
+    its ancestry row names. Step 1 runs eagerly, the generic step is captured once and replayed on one stream; the
+    host reads the count of documents not done every `check_every` steps."""
+
+    def __init__(self, engine, z, max_length, num_beams, start_token, end_token, *, length_penalty=1.0,
+                 repetition_penalty=1.0, use_graph=True, history=False):
+        dev = engine.P.device
+        if dev.type != 'cuda':
+            raise RuntimeError('BeamDecoder runs on the MI355X kernels: pass a GPU engine (no CPU fallback)')
+        B = z.shape[0]
+        self.beam = BeamState(B, num_beams, max_length, start_token, end_token, length_penalty, dev, history=history)
+        self.W, self.docs = self.beam.W, B
+        self.repetition_penalty = float(repetition_penalty)
+        # KVDecoder reads the id rows and the position through its state
+        state = SimpleNamespace(output_ids=self.beam.ids, cur=self.beam.cur)
+        zr = z.reshape(B, -1).to(dev, f32).repeat_interleave(self.W, dim=0)
+        super().__init__(engine, state, zr, use_graph=use_graph)
+        if self.V < 2 * self.W:
+            raise ValueError(f'num_beams {self.W}: the vocabulary has {self.V} entries (2 * num_beams at least)')
+
+    def _attn(self, i):
+        K.beam_attn(self.qkv, self.kc[i], self.vc[i], self.beam.anc, self.O, self.B, self.W, self.H, self.hd, self.T,
+                    self.beam.cur, self.window)
+
+    def _choose(self):
+        bs, R = self.beam, self.B
+        if self.repetition_penalty > 1.0:
+            K.dec_penalty(self.logits, R, None, bs.ids, self.T, bs.cur, None, self.repetition_penalty)
+        K.beam_topk(self.logits, self.V, R, self.W, bs.cum, bs.done, bs.cand_score, bs.cand_tok)
+        K.beam_select(bs.cand_score, bs.cand_tok, bs)
+        K.dec_advance(bs.cur)
+
+    def run(self, num_return=1, check_every=8):
+        bs, T = self.beam, self.T
+        if not 1 <= num_return <= self.W:
+            raise ValueError(f'num_return {num_return}: 1..num_beams ({self.W})')
+        self._step(first=True)
+        c, n = 2, 0                                  # c mirrors *cur: the index of the token the next step generates
+        while c <= T - 2:
+            if n % check_every == 0 and int(bs.not_done.item()) == 0:
+                break
+            if self.use_graph:
+                if self.graph is None:
+                    self._capture()
+                self.graph.replay()
+            else:
+                self._step(first=False)
+            c += 1
+            n += 1
+        self.steps = c - 1
+        return BeamResult(*K.beam_finalize(bs, int(num_return)), bs.history())
+
+    def _capture(self):
+        """Capture one generic step on one stream. The warm-up launch advances the device state, so it is saved and
+        restored around the capture; the KV caches are not part of it: the warm-up wrote, in every row at the
+        current position, what the first replay writes again from the same restored state."""
+        state = self.beam.tensors()
+        saved = [t.clone() for t in state]
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self._step(first=False)          # warm-up outside the graph
+        torch.cuda.current_stream().wait_stream(s)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._step(first=False)
         for t, v in zip(state, saved):
             t.copy_(v)
         self.graph = g

@@ -851,6 +851,71 @@ def slot_refill(pos, key, ids, T, S, start_token, z_all, z_slot, num_samples, ne
                                stream()), 'svae_slot_refill')
 
 
+# ---- beam search decoding (R = B * W rows; the state buffers of decoding.BeamState)
+def beam_attn(qkv, kc, vc, anc, O, R, W, H, hd, T, cur, window, scale=None, ldq=None, ldo=None):
+    """svae_beam_attn: dec_attn reading key j < p of row r from cache row (r // W) * W + anc[r][j]."""
+    _dev(qkv, kc, vc, anc, O, cur)
+    assert anc.dtype == torch.uint8 and anc.is_contiguous() and anc.numel() >= R * T
+    assert kc.numel() >= R * H * T * hd and vc.numel() >= R * H * T * hd
+    check(lib.svae_beam_attn(qkv.data_ptr(), ldq or 3 * H * hd, kc.data_ptr(), vc.data_ptr(), anc.data_ptr(), R, W, H,
+                             hd, T, cur.data_ptr(), window, hd ** -0.5 if scale is None else scale, O.data_ptr(),
+                             ldo or H * hd, stream()), 'svae_beam_attn')
+
+
+def beam_topk(logits, V, R, W, cum, done, cand_score, cand_tok):
+    """svae_beam_topk: cand_score f32 / cand_tok int32 [R, 2W] of the rows with cum > -inf whose document is live."""
+    _dev(logits, cum, cand_score, cand_tok)
+    assert logits.dtype == f32 and logits.stride(1) == 1 and logits.shape[0] >= R and logits.shape[1] >= V
+    assert cum.dtype == f32 and cum.numel() >= R and (done is None or (done.dtype == torch.uint8 and done.numel() * W >= R))
+    assert cand_score.dtype == f32 and cand_tok.dtype == torch.int32
+    assert cand_score.is_contiguous() and cand_tok.is_contiguous() and min(cand_score.numel(), cand_tok.numel()) >= R * 2 * W
+    check(lib.svae_beam_topk(logits.data_ptr(), logits.stride(0), V, R, W, cum.data_ptr(), ptr(done),
+                             cand_score.data_ptr(), cand_tok.data_ptr(), stream()), 'svae_beam_topk')
+
+
+def _beam_state(st):
+    B, W, T = st.B, st.W, st.T
+    R = B * W
+    for t, dt, n in ((st.cum, f32, R), (st.ids, torch.int64, R * T), (st.anc, torch.uint8, R * T),
+                     (st.ids_next, torch.int64, R * T), (st.anc_next, torch.uint8, R * T), (st.len_pen, f32, T),
+                     (st.pool_score, f32, R), (st.pool_logp, f32, R), (st.pool_len, torch.int32, R),
+                     (st.pool_ids, torch.int64, R * T), (st.pool_n, torch.int32, B), (st.done, torch.uint8, B),
+                     (st.not_done, torch.int32, 1), (st.stamp, torch.int32, B), (st.cur, torch.int32, 1)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= n
+    for t, dt in ((st.hist_parent, torch.int32), (st.hist_token, torch.int32), (st.hist_score, f32)):
+        assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= T * R)
+
+
+def beam_select(cand_score, cand_tok, st):
+    """svae_beam_select on a decoding.BeamState: one step's selection, pool update and commit."""
+    _beam_state(st)
+    R = st.B * st.W
+    assert cand_score.dtype == f32 and cand_tok.dtype == torch.int32
+    assert cand_score.is_contiguous() and cand_tok.is_contiguous()
+    assert min(cand_score.numel(), cand_tok.numel()) >= R * 2 * st.W
+    check(lib.svae_beam_select(cand_score.data_ptr(), cand_tok.data_ptr(), st.cum.data_ptr(), st.ids.data_ptr(),
+                               st.anc.data_ptr(), st.ids_next.data_ptr(), st.anc_next.data_ptr(), st.B, st.W, st.T,
+                               st.cur.data_ptr(), st.end_token, st.len_pen.data_ptr(), 1 if st.alpha > 0 else 0,
+                               st.pool_score.data_ptr(), st.pool_logp.data_ptr(), st.pool_len.data_ptr(),
+                               st.pool_ids.data_ptr(), st.pool_n.data_ptr(), st.done.data_ptr(),
+                               st.not_done.data_ptr(), st.stamp.data_ptr(), ptr(st.hist_parent), ptr(st.hist_token),
+                               ptr(st.hist_score), stream()), 'svae_beam_select')
+
+
+def beam_finalize(st, n):
+    """svae_beam_finalize -> (ids int64 [B, n, T - 1], scores f32 [B, n], log_probs f32 [B, n], lengths int32 [B, n])."""
+    _beam_state(st)
+    B, T, dev = st.B, st.T, st.cum.device
+    ids = torch.empty(B, n, T - 1, device=dev, dtype=torch.int64)
+    scores, logp = torch.empty(B, n, device=dev, dtype=f32), torch.empty(B, n, device=dev, dtype=f32)
+    lengths = torch.empty(B, n, device=dev, dtype=torch.int32)
+    check(lib.svae_beam_finalize(st.cum.data_ptr(), st.ids.data_ptr(), B, st.W, T, st.len_pen.data_ptr(),
+                                 st.pool_score.data_ptr(), st.pool_logp.data_ptr(), st.pool_len.data_ptr(),
+                                 st.pool_ids.data_ptr(), st.pool_n.data_ptr(), st.done.data_ptr(), n, ids.data_ptr(),
+                                 scores.data_ptr(), logp.data_ptr(), lengths.data_ptr(), stream()), 'svae_beam_finalize')
+    return ids, scores, logp, lengths
+
+
 def _latent_rows(*ts):
     """The [rows, Z] f32 operands of the latent kernels: contiguous device tensors of one shape."""
     _dev(*ts)

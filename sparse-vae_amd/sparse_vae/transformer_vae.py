@@ -25,9 +25,9 @@ from .core import (ContinuousVAEHparams, ContinuousVAEHooks, ConditionalGaussian
 from .core.padded_tensor import PaddedTensor
 from .engine import FlatParams, VAEEngine
 from .core.generation import GenerationState
-from .decoding import KVDecoder, StreamDecoder
+from .decoding import BeamDecoder, KVDecoder, StreamDecoder
 from . import kernels as K
-from ._native import EPI_F32, EPI_BF16
+from ._native import BEAM_MAX_W, EPI_F32, EPI_BF16
 
 
 @dataclass
@@ -501,6 +501,33 @@ class TransformerVAE(ContinuousVAEHooks, LanguageModel):
         return out
 
     @torch.no_grad()
+    def beam_search(self, max_length: int, z, num_beams: int = 4, length_penalty: float = 1.0, num_return: int = 1,
+                    repetition_penalty: float = 1.0, use_graph: bool = True, return_history: bool = False):
+        """The most probable continuations under p(x|z) by beam search (BeamDecoder): z [B, 1, latent],
+        num_beams hypotheses per document (1..16), at most max_length - 2 generated tokens as in `sample`. A finished
+        hypothesis scores log p / length ** length_penalty, the end token counted. Deterministic: no seed, ties
+        decided by (score, beam, token). Returns a BeamResult: ids int64 [B, num_return, max_length - 1] (start token
+        excluded, zero after the end token), scores, log_probs f32 and lengths int32 [B, num_return], best first;
+        with return_history the parent / token / score of every step's rows. Raises below kl_weight 1."""
+        if self.hparams.kl_weight < 1.0:
+            raise RuntimeError(f'beam_search: the model does not sample below kl_weight 1 (it is '
+                               f'{self.hparams.kl_weight})')
+        num_beams, num_return = int(num_beams), int(num_return)
+        if not 1 <= num_beams <= BEAM_MAX_W:
+            raise ValueError(f'beam_search: num_beams {num_beams} (1..{BEAM_MAX_W})')
+        if not 1 <= num_return <= num_beams:
+            raise ValueError(f'beam_search: num_return {num_return} (1..num_beams = {num_beams})')
+        eng = self._require_engine()
+        start = self.start_token if self.start_token is not None else 1      # [CLS] (text_data_module.py:271)
+        end = self.end_token if self.end_token is not None else 2            # [SEP]
+        dec = BeamDecoder(eng, z.to(self.device), int(max_length), num_beams, start, end,
+                          length_penalty=float(length_penalty), repetition_penalty=float(repetition_penalty),
+                          use_graph=use_graph, history=return_history)
+        out = dec.run(num_return=num_return)
+        self.last_beam_steps = dec.steps                                     # for scripts/bench_beam.py
+        return out
+
+    @torch.no_grad()
     def embed(self, ids):
         """input_layer(ids) as a PaddedTensor (the reference's x, transformer_vae.py:45)."""
         pad = getattr(ids, 'padding', None)
@@ -534,13 +561,16 @@ class TransformerVAE(ContinuousVAEHooks, LanguageModel):
 
     @torch.no_grad()
     def autoencode(self, batch, max_length: Optional[int] = None, sample_posterior: bool = False,
-                   slots: Optional[int] = None, seed: int = 0, **gen):
+                   slots: Optional[int] = None, seed: int = 0, num_beams: Optional[int] = None,
+                   length_penalty: float = 1.0, **gen):
         """Reconstruct a batch through its latent (reconstruct.py:31-32 at corpus scale): q(z|x) from `encode`, z its
         mean (or, with sample_posterior, one draw through svae_latent_draw keyed by `seed`), then
         `sample_stream(max_length, B, z=z, **gen)`. Returns (ids int16 [B, max_length - 1] on the device, zero after
         each row's end, and the posterior). max_length defaults to the batch's width + 1; gen takes GenerationState's
-        settings, with temperature 0.7 (reconstruct.py:32) unless given. Raises below kl_weight 1, where the model
-        does not sample."""
+        settings, with temperature 0.7 (reconstruct.py:32) unless given. With num_beams the latent is decoded by
+        `beam_search(max_length, z, num_beams, length_penalty)` instead and each row is its best hypothesis (the same
+        int16 rows; of gen only repetition_penalty applies, default 1.0; the whole BeamResult stays in
+        `last_beam_result`). Raises below kl_weight 1, where the model does not sample."""
         if self.hparams.kl_weight < 1.0:
             raise RuntimeError(f'autoencode: the model does not sample below kl_weight 1 (it is '
                                f'{self.hparams.kl_weight})')
@@ -553,5 +583,10 @@ class TransformerVAE(ContinuousVAEHooks, LanguageModel):
         if sample_posterior:
             z = K.latent_draw(posterior.loc.reshape(B, Z).contiguous(), posterior.scale.reshape(B, Z).contiguous(),
                               seed=seed).view(B, 1, Z)
+        if num_beams is not None:
+            res = self.beam_search(int(max_length), z, num_beams=num_beams, length_penalty=length_penalty,
+                                   repetition_penalty=gen.get('repetition_penalty', 1.0))
+            self.last_beam_result = res
+            return res.ids[:, 0].to(torch.int16), posterior
         gen.setdefault('temperature', 0.7)
         return self.sample_stream(int(max_length), B, slots=slots, z=z, **gen), posterior
