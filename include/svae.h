@@ -754,6 +754,80 @@ int64_t svae_kmeans_seed_ws_bytes(int32_t N, int32_t K, int32_t Z);
 int svae_kmeans_seed(const float* x, int32_t N, int32_t K, int32_t Z, const float* u, uint64_t seed, int32_t* rows,
                      float* cent, void* ws, int64_t ws_bytes, svae_stream_t stream);
 
+/* ---- a Gaussian-mixture prior of the latents: EM over the index, a density and a sampler (csrc/gmm.hip; it stands
+ * where the reference has only torch.randn at transformer_vae.py:103) ---------------------------------------------------
+ * The mixture has K diagonal components. A row is the Gaussian q_i = N(x_i, diag(s2_i)) (x the posterior mean, s2 the
+ * posterior variance), or the point x_i when s2 is NULL. With
+ *   a_ik = log pi_k - 1/2 sum_d [log(2 pi v_kd) + ((x_id - m_kd)^2 + s2_id) / v_kd]      (= E_{q_i} log pi_k N(z; m_k, v_k))
+ * EM ascends L = (1 / N) sum_i logsumexp_k a_ik, a lower bound (Jensen) on the aggregate posterior's expected
+ * log-density under the mixture; for points it is the log-likelihood and this is the textbook diagonal GMM.
+ * x and s2 are f32 [N][Z], 16-byte aligned; Z a multiple of 4 in 4..256; 1 <= K <= SVAE_GMM_MAX_K; 1 <= N <= 2^24.
+ * Every entry point returns 1 before any launch on a NULL required operand, a misaligned pointer, a shape out of
+ * range or a workspace that is too small; the *_ws_bytes companions and svae_gmm_params_floats return 0 on a bad shape.
+ * ws: caller-owned, 8-byte aligned, contents need not survive. Nothing below uses an atomic: grids and summation
+ * orders depend on (N, K, Z) alone, so two calls on one input agree bit for bit. Rows and parameters must be finite.
+ * params: one device block of SVAE_GMM_PARAM_FLOATS(K, Z) floats per model, 16-byte aligned, with KP = K rounded up to
+ *   a multiple of 4: weight [KP] at 0, logc [KP] at KP, then mean, var, inv_var, sd, f32 [K][Z] each, at 2 KP + j K Z
+ *   (SVAE_GMM_OFF_*). weight, mean and var are the model; inv_var = (float)(1 / (double)var), sd =
+ *   (float)sqrt((double)var) and logc = log pi_k - 1/2 sum_d log(2 pi v_kd) (formed in f64 in ascending d, rounded
+ *   once; -inf for pi_k = 0) are derived.
+ * svae_gmm_prepare: the derived rows from (weight, mean, var), for a loaded or hand-made model. svae_gmm_mstep's last
+ *   launch calls the same device function.
+ * a_ik in f32 from direct differences: per float4 chunk of the row d = x - m, e = fmaf(d, d, s2) (s2 = 0 for points),
+ *   two fmaf chains s = fmaf(e, inv_var, s) (elements 0, 2 and elements 1, 3 of the chunks, in chunk order), q their
+ *   sum, a = fmaf(-0.5, q, logc); logc = -inf gives a = -inf whatever q is. The order depends on Z alone, contraction
+ *   is off, and every kernel shares the function: a (row, component) pair has one f32 value.
+ *   |error| <= ((Z / 2 + 5) q / 2 + |logc| + |a|) 2^-24 to first order, against f64 from the same (x, s2, weight,
+ *   mean, var).
+ * svae_gmm_estep: lse f32 [N] = logsumexp_k a_ik, carried online over the components in index order ((M, S) from
+ *   (-inf, 0); a = -inf is skipped, so a component of weight 0 contributes exactly 0; a > M: S = fmaf(S, expf(M - a),
+ *   1), M = a; else S += expf(a - M); lse = M + logf(S)); a NaN a_ik makes lse_i NaN. label int32 [N] or NULL: the
+ *   largest a_ik wins, ties go to the lower index, a NaN loses to every number, an all-NaN row gets 0. resp f32 [N][K]
+ *   or NULL: expf(a_ik - lse_i). bound f64 [1] = sum_i lse_i, added in f64 in a fixed order. A workgroup owns
+ *   SVAE_GMM_ROWS_PER_BLOCK rows (a lane holds its row, and its s2 row, in registers; with s2 and Z > 128 in four
+ *   segments of 64 per tile) and streams (mean, inv_var, logc) through LDS in tiles of SVAE_GMM_TILE_COMPONENTS.
+ *   ws >= svae_gmm_estep_ws_bytes = row blocks * 8 bytes.
+ * svae_gmm_mstep: one EM M-step in place on params. Exactly one of lse (soft: r_ik = expf(a_ik - lse_i), a_ik from the
+ *   function above) and label (hard: r_ik = 1 where label_i == k; labels outside 0..K-1 are ignored) is non-NULL. In
+ *   f64 and relative to the mean on entry (d = x - m in f32, widened): N_k = sum r, S1 = sum r d, S2 = sum r (d^2 +
+ *   s2). The rows are cut into G groups of consecutive rows (svae_gmm_geometry: from (N, K) alone); a group adds its
+ *   rows in ascending order, then the groups are added in ascending order. m = m_old + S1 / N_k, v = S2 / N_k -
+ *   (S1 / N_k)^2 + reg_covar, pi_k = N_k / (the sum of the positive N_k in index order), in f64, rounded once; then
+ *   the derived rows. A component with N_k not > 0 keeps its mean and variance and gets weight 0. nk f64 [K]: N_k.
+ *   reg_covar >= 0. ws >= svae_gmm_mstep_ws_bytes = (G + 1) * K * (2 Z + 1) * 8 bytes with G = ceil(N / rows per
+ *   group), rows per group = ceil(N / max(1, 16384 / K)) rounded up to 64: at most 16384 + K statistics rows, 66 MiB
+ *   at N = 2^24, K = 256, Z = 256.
+ * svae_gmm_sample: comp int32 [n], z f32 [n][Z], 1 <= n <= 2^24. u f32 [n] or NULL: the uniforms in [0, 1), injected
+ *   or drawn from the library's counter RNG keyed by (seed ^ 0x636F6D706F6E656E, row). Row j takes the first k with
+ *   cum_k > (double)u_j * cum_{K-1}, cum the inclusive prefix sums of the weights in f64 in index order (a weight that
+ *   is not > 0 adds nothing, so it is never drawn), clamped to the last component of positive weight. z_jd =
+ *   fmaf(sd_kd, eps_jd, mean_kd); eps f32 [n][Z] or NULL: svae_latent_draw's normals (keyed by (seed, row, column)),
+ *   so one standard-normal component reproduces svae_latent_draw(0, 1) bit for bit.
+ * svae_gmm_geometry: geom (HOST int32 [6]) = {E-step rows per workgroup, row blocks, component tile, M-step row
+ *   groups G, rows per group, E-step row segments (4 with s2 at Z > 128, else 1)}. */
+#define SVAE_GMM_MAX_K 256
+#define SVAE_GMM_TILE_COMPONENTS 16
+#define SVAE_GMM_ROWS_PER_BLOCK 256
+#define SVAE_GMM_KPAD(K) (((int64_t)(K) + 3) / 4 * 4)
+#define SVAE_GMM_OFF_WEIGHT(K, Z) ((int64_t)0)
+#define SVAE_GMM_OFF_LOGC(K, Z) SVAE_GMM_KPAD(K)
+#define SVAE_GMM_OFF_MEAN(K, Z) (2 * SVAE_GMM_KPAD(K))
+#define SVAE_GMM_OFF_VAR(K, Z) (2 * SVAE_GMM_KPAD(K) + (int64_t)(K) * (Z))
+#define SVAE_GMM_OFF_INV_VAR(K, Z) (2 * SVAE_GMM_KPAD(K) + 2 * (int64_t)(K) * (Z))
+#define SVAE_GMM_OFF_SD(K, Z) (2 * SVAE_GMM_KPAD(K) + 3 * (int64_t)(K) * (Z))
+#define SVAE_GMM_PARAM_FLOATS(K, Z) (2 * SVAE_GMM_KPAD(K) + 4 * (int64_t)(K) * (Z))
+int64_t svae_gmm_params_floats(int32_t K, int32_t Z);
+int svae_gmm_geometry(int32_t N, int32_t K, int32_t Z, int32_t has_s2, int32_t* geom);
+int svae_gmm_prepare(float* params, int32_t K, int32_t Z, svae_stream_t stream);
+int64_t svae_gmm_estep_ws_bytes(int32_t N, int32_t K, int32_t Z);
+int svae_gmm_estep(const float* x, const float* s2, int32_t N, const float* params, int32_t K, int32_t Z, float* lse,
+                   int32_t* label, float* resp, double* bound, void* ws, int64_t ws_bytes, svae_stream_t stream);
+int64_t svae_gmm_mstep_ws_bytes(int32_t N, int32_t K, int32_t Z);
+int svae_gmm_mstep(const float* x, const float* s2, int32_t N, const float* lse, const int32_t* label, float* params,
+                   int32_t K, int32_t Z, float reg_covar, double* nk, void* ws, int64_t ws_bytes, svae_stream_t stream);
+int svae_gmm_sample(const float* params, int32_t K, int32_t Z, int32_t n, const float* u, const float* eps,
+                    uint64_t seed, float* z, int32_t* comp, svae_stream_t stream);
+
 /* ---- reconstruction scoring over token ids: the integer counts behind BLEU, token accuracy and the edit rate of P
  * (candidate, reference) pairs (csrc/textscore.hip; what stands in for reconstruction_bleu of math_utils.py:9-38, whose
  * keys past its second order are not n-grams) --------------------------------------------------------------------------

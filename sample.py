@@ -9,6 +9,11 @@ The default path is TransformerVAE.sample_stream: --slots decoder rows, each ref
 sample as soon as its current one ends. --loop runs the reference's batch-synchronous loop instead
 (batch_generate_samples over model.sample at batch size --slots), for comparison.
 
+--prior prior.npz (written by fit_prior.py) draws z from that Gaussian mixture instead of N(0, I) and passes it as z=
+to sample_stream, or to model.sample under --loop; the component draw and the normals are seeded from --seed. The .npz
+then also holds `components` int32 [N], the mixture component behind each sample, and the prior's path among the
+generation settings. Without --prior nothing changes, the .npz's keys included.
+
 Model configuration is as for train.py and gather_latents.py: an OmegaConf-style dotlist (model.*) and a named preset
 merged after it. Without --weights the model keeps its initial weights (useful only to try the pipeline):
     python sample.py --preset tiny --num-samples 40 --slots 8 --max-length 32 --out /tmp/samples.npz
@@ -40,6 +45,7 @@ def build_parser():
     ap.add_argument('--start-token', type=int, default=None, help='default: the model\'s ([CLS] = 1)')
     ap.add_argument('--end-token', type=int, default=None, help='default: the model\'s ([SEP] = 2)')
     ap.add_argument('--seed', type=int, default=None, help='torch.manual_seed before sampling')
+    ap.add_argument('--prior', default=None, help='mixture .npz of fit_prior.py: draw z from it instead of N(0, I)')
     ap.add_argument('--loop', action='store_true', help='the batch-synchronous loop over model.sample')
     ap.add_argument('--device', default=None, help="torch device (default: 'cuda')")
     ap.add_argument('overrides', nargs='*', help='model.key=value, as for train.py')
@@ -67,7 +73,28 @@ def main(argv=None):
     if args.seed is not None:
         torch.manual_seed(args.seed)
     N, T = args.num_samples, args.max_length
-    if args.loop:
+    comp = None
+    if args.prior:
+        from sparse_vae import GaussianMixture
+        prior = GaussianMixture.load(args.prior, model.device)
+        if prior.means_.shape[1] != model.hparams.latent_depth:
+            raise SystemExit(f'{args.prior} has rows of {prior.means_.shape[1]}, the model a latent depth of '
+                             f'{model.hparams.latent_depth}')
+        z, comp = prior.sample(N, seed=args.seed or 0)
+    if args.prior and args.loop:
+        bs, start = min(args.slots, max(N, 1)), [0]
+
+        def next_batch():                            # the last batch may be short: the helper truncates anyway
+            zb = z[start[0]:start[0] + bs]
+            start[0] += bs
+            return model.sample(T, zb.shape[0], z=zb, **gen)
+        rows = batch_generate_samples(next_batch, N, T, end)
+    elif args.prior:
+        out = model.sample_stream(T, N, slots=min(args.slots, max(N, 1)), z=z, **gen)
+        if out is None:
+            raise SystemExit('the model does not sample below kl_weight 1')
+        rows = trim_samples(out, end)
+    elif args.loop:
         rows = batch_generate_samples(partial(model.sample, T, min(args.slots, max(N, 1)), **gen), N, T, end)
     else:
         out = model.sample_stream(T, N, slots=min(args.slots, max(N, 1)), **gen)
@@ -80,7 +107,11 @@ def main(argv=None):
     lengths = np.array([len(r) for r in rows], dtype=np.int32)
     hparams = dict(model=dict(config['model']), generation=dict(gen, max_length=T, slots=args.slots, end_token=end,
                                                                 seed=args.seed, loop=bool(args.loop)))
-    np.savez(args.out, ids=ids, lengths=lengths, hparams=json.dumps(hparams, default=str))
+    extra = {}
+    if args.prior:
+        hparams['generation']['prior'] = args.prior
+        extra['components'] = comp.cpu().numpy().astype(np.int32)
+    np.savez(args.out, ids=ids, lengths=lengths, hparams=json.dumps(hparams, default=str), **extra)
     print(f'{N} samples (mean length {lengths.mean() if N else 0:.1f}) -> {args.out}')
     return ids, lengths
 

@@ -28,6 +28,8 @@ PAIR_KINDS = {'rbf': PAIR_RBF, 'imq': PAIR_IMQ}
 PAIRSUM_TILE_COLS, PAIRSUM_MAX_P, MMD_REDUCE_BLOCKS = 32, 8, 256   # SVAE_PAIRSUM_TILE_COLS, _MAX_P, SVAE_MMD_REDUCE_BLOCKS
 # SVAE_KMEANS_MAX_K, _TILE_CENTROIDS, _SORT_BLOCKS, _SEED_BLOCK_ROWS
 KMEANS_MAX_K, KMEANS_TILE_CENTROIDS, KMEANS_SORT_BLOCKS, KMEANS_SEED_BLOCK_ROWS = 1024, 32, 256, 256
+# SVAE_GMM_MAX_K, _TILE_COMPONENTS, _ROWS_PER_BLOCK
+GMM_MAX_K, GMM_TILE_COMPONENTS, GMM_ROWS_PER_BLOCK = 256, 16, 256
 TEXT_MAX_LEN = 2048                                  # SVAE_TEXT_MAX_LEN
 BEAM_MAX_W = 16                                      # SVAE_BEAM_MAX_W
 
@@ -238,6 +240,17 @@ _SIGS = {
     'svae_kmeans_seed_ws_bytes': [c_int32, c_int32, c_int32],
     'svae_kmeans_seed': [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
                          c_int64, c_void_p],
+    'svae_gmm_params_floats': [c_int32, c_int32],
+    'svae_gmm_geometry': [c_int32, c_int32, c_int32, c_int32, c_void_p],
+    'svae_gmm_prepare': [c_void_p, c_int32, c_int32, c_void_p],
+    'svae_gmm_estep_ws_bytes': [c_int32, c_int32, c_int32],
+    'svae_gmm_estep': [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                       c_void_p, c_int64, c_void_p],
+    'svae_gmm_mstep_ws_bytes': [c_int32, c_int32, c_int32],
+    'svae_gmm_mstep': [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p,
+                       c_void_p, c_int64, c_void_p],
+    'svae_gmm_sample': [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
+                        c_void_p],
     'svae_ngram_overlap': [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p],
     'svae_edit_distance': [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p],
     'svae_version': [],
@@ -260,6 +273,8 @@ def _load():
                       'svae_latent_colstats_ws_bytes': c_int64,
                       'svae_kmeans_assign_ws_bytes': c_int64, 'svae_kmeans_update_ws_bytes': c_int64,
                       'svae_kmeans_seed_ws_bytes': c_int64,
+                      'svae_gmm_params_floats': c_int64, 'svae_gmm_estep_ws_bytes': c_int64,
+                      'svae_gmm_mstep_ws_bytes': c_int64,
                       'svae_gemm_group_table_bytes': c_int64}.get(name, ctypes.c_int)
     return lib
 

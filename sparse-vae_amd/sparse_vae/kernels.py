@@ -1309,3 +1309,127 @@ def edit_distance(cand, ref, cand_len, ref_len, out=None):
     check(lib.svae_edit_distance(cand.data_ptr(), cand.shape[1], ref.data_ptr(), ref.shape[1], cand_len.data_ptr(),
                                  ref_len.data_ptr(), P, out.data_ptr(), stream()), 'svae_edit_distance')
     return out
+
+
+def gmm_param_offsets(K, Z):
+    """The float offsets of a svae_gmm parameter block (include/svae.h's SVAE_GMM_OFF_*): dict name -> (offset, shape),
+    plus 'floats', the block's length."""
+    kp, kz = (K + 3) // 4 * 4, K * Z
+    out = {'weight': (0, (K,)), 'logc': (kp, (K,))}
+    for j, name in enumerate(('mean', 'var', 'inv_var', 'sd')):
+        out[name] = (2 * kp + j * kz, (K, Z))
+    out['floats'] = 2 * kp + 4 * kz
+    assert out['floats'] == lib.svae_gmm_params_floats(K, Z)
+    return out
+
+
+def gmm_view(params, K, Z, name):
+    """The view of row `name` ('weight', 'logc', 'mean', 'var', 'inv_var', 'sd') inside a parameter block."""
+    off, shape = gmm_param_offsets(K, Z)[name]
+    n = 1
+    for d in shape:
+        n *= d
+    return params[off:off + n].view(shape)
+
+
+def _gmm_shape(x, s2, params, K, name):
+    n, Z = _mmd_rows(x, f'{name} x')
+    if s2 is not None:
+        _latent_rows(x, s2)
+    if not 1 <= K <= N.GMM_MAX_K:
+        raise ValueError(f'{name}: 1 <= K <= {N.GMM_MAX_K}, got {K}')
+    _kmeans_vec(params, f32, lib.svae_gmm_params_floats(K, Z), 'params')
+    return n, Z
+
+
+def gmm_geometry(n, K, Z, has_s2=False):
+    """svae_gmm_geometry: (E-step rows per workgroup, row blocks, component tile, M-step row groups, rows per group,
+    E-step row segments)."""
+    geom = (ctypes.c_int32 * 6)()
+    check(lib.svae_gmm_geometry(n, K, Z, int(bool(has_s2)), ctypes.addressof(geom)), 'svae_gmm_geometry')
+    return tuple(geom)
+
+
+def gmm_pack(weight, mean, var):
+    """A parameter block from weight [K], mean [K, Z], var [K, Z] device tensors, derived rows included
+    (svae_gmm_prepare)."""
+    _dev(weight, mean, var)
+    K, Z = mean.shape
+    if Z % 4 or not 4 <= Z <= 256 or not 1 <= K <= N.GMM_MAX_K:
+        raise ValueError(f'gmm_pack: Z a multiple of 4 in 4..256 and 1 <= K <= {N.GMM_MAX_K}, got K = {K}, Z = {Z}')
+    assert weight.shape == (K,) and var.shape == (K, Z)
+    params = torch.zeros(gmm_param_offsets(K, Z)['floats'], dtype=f32, device=mean.device)
+    gmm_view(params, K, Z, 'weight').copy_(weight)
+    gmm_view(params, K, Z, 'mean').copy_(mean)
+    gmm_view(params, K, Z, 'var').copy_(var)
+    return gmm_prepare(params, K, Z)
+
+
+def gmm_prepare(params, K, Z):
+    """svae_gmm_prepare, in place: the derived rows (inv_var, sd, logc) of a block from its (weight, mean, var)."""
+    _kmeans_vec(params, f32, lib.svae_gmm_params_floats(K, Z), 'params')
+    check(lib.svae_gmm_prepare(params.data_ptr(), K, Z, stream()), 'svae_gmm_prepare')
+    return params
+
+
+def gmm_estep(x, s2, params, K, lse=None, label=None, resp=None, bound=None, want_label=True, want_resp=False):
+    """svae_gmm_estep: rows x (and their variances s2, or None for points) f32 [N, Z] against a K-component block ->
+    (lse f32 [N], label int32 [N] or None, resp f32 [N, K] or None, bound f64 [1] = sum lse). The workspace is
+    allocated per call (stream-ordered by the caching allocator)."""
+    n, Z = _gmm_shape(x, s2, params, K, 'gmm_estep')
+    dev = x.device
+    lse = torch.empty(n, dtype=f32, device=dev) if lse is None else lse
+    _kmeans_vec(lse, f32, n, 'lse')
+    if label is None and want_label:
+        label = torch.empty(n, dtype=torch.int32, device=dev)
+    if label is not None:
+        _kmeans_vec(label, torch.int32, n, 'label')
+    if resp is None and want_resp:
+        resp = torch.empty(n, K, dtype=f32, device=dev)
+    if resp is not None:
+        _kmeans_vec(resp, f32, n * K, 'resp')
+    bound = torch.empty(1, dtype=torch.float64, device=dev) if bound is None else bound
+    _kmeans_vec(bound, torch.float64, 1, 'bound')
+    nbytes = lib.svae_gmm_estep_ws_bytes(n, K, Z)
+    ws = _kmeans_ws(nbytes, dev)
+    check(lib.svae_gmm_estep(x.data_ptr(), ptr(s2), n, params.data_ptr(), K, Z, lse.data_ptr(), ptr(label), ptr(resp),
+                             bound.data_ptr(), ws.data_ptr(), nbytes, stream()), 'svae_gmm_estep')
+    return lse, label, resp, bound
+
+
+def gmm_mstep(x, s2, params, K, lse=None, label=None, reg_covar=1e-6, nk=None):
+    """svae_gmm_mstep, in place on params: one M-step from the soft responsibilities expf(a - lse) (lse f32 [N]) or
+    from hard labels (int32 [N]); exactly one of the two. -> nk f64 [K]."""
+    n, Z = _gmm_shape(x, s2, params, K, 'gmm_mstep')
+    if (lse is None) == (label is None):
+        raise ValueError('gmm_mstep: exactly one of lse (soft) and label (hard)')
+    if lse is not None:
+        _kmeans_vec(lse, f32, n, 'lse')
+    else:
+        _kmeans_vec(label, torch.int32, n, 'label')
+    dev = x.device
+    nk = torch.empty(K, dtype=torch.float64, device=dev) if nk is None else nk
+    _kmeans_vec(nk, torch.float64, K, 'nk')
+    nbytes = lib.svae_gmm_mstep_ws_bytes(n, K, Z)
+    ws = _kmeans_ws(nbytes, dev)
+    check(lib.svae_gmm_mstep(x.data_ptr(), ptr(s2), n, ptr(lse), ptr(label), params.data_ptr(), K, Z, float(reg_covar),
+                             nk.data_ptr(), ws.data_ptr(), nbytes, stream()), 'svae_gmm_mstep')
+    return nk
+
+
+def gmm_sample(params, K, Z, n, seed=0, u=None, eps=None):
+    """svae_gmm_sample: n draws -> (z f32 [n, Z], comp int32 [n]). u f32 [n] and eps f32 [n, Z] are injected, or drawn
+    from the counter RNG keyed by seed (eps exactly as latent_draw draws it)."""
+    _kmeans_vec(params, f32, lib.svae_gmm_params_floats(K, Z), 'params')
+    if not 1 <= n <= 2 ** 24:
+        raise ValueError(f'gmm_sample: 1..2^24 rows, got {n}')
+    dev = params.device
+    if u is not None:
+        _kmeans_vec(u, f32, n, 'u')
+    if eps is not None:
+        _kmeans_vec(eps, f32, n * Z, 'eps')
+    z = torch.empty(n, Z, dtype=f32, device=dev)
+    comp = torch.empty(n, dtype=torch.int32, device=dev)
+    check(lib.svae_gmm_sample(params.data_ptr(), K, Z, n, ptr(u), ptr(eps), int(seed) & (2 ** 64 - 1), z.data_ptr(),
+                              comp.data_ptr(), stream()), 'svae_gmm_sample')
+    return z, comp

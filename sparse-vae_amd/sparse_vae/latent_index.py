@@ -238,6 +238,18 @@ class LatentIndex:
         from .kmeans import KMeans
         return KMeans(n_clusters, **kw).fit(self)
 
+    def fit_mixture(self, n_components: int, source: str = 'posterior', **kw):
+        """A Gaussian-mixture prior of the index (svae_gmm_*): GaussianMixture(n_components, **kw) fitted to the
+        posteriors N(loc, scale^2) ('posterior', the default) or to the means as points ('mean': a collapsed dimension
+        then gets a variance of about reg_covar, see sparse_vae.mixture)."""
+        from .mixture import GaussianMixture
+        if source not in ('posterior', 'mean'):
+            raise ValueError(f"source must be 'posterior' or 'mean', got {source!r}")
+        gm = GaussianMixture(n_components, **kw)
+        if source == 'posterior' or len(self) == 0 or self.device is None or self.device.type != 'cuda':
+            return gm.fit(self)          # the empty and the CPU index are refused there
+        return gm.fit(self.loc.contiguous())
+
     # ------------------------------------------------------------------ persistence
     def save(self, path):
         """One .npz: loc, scale, titles. The derived rows are not stored (load recomputes them)."""
