@@ -828,6 +828,76 @@ int svae_gmm_mstep(const float* x, const float* s2, int32_t N, const float* lse,
 int svae_gmm_sample(const float* params, int32_t K, int32_t Z, int32_t n, const float* u, const float* eps,
                     uint64_t seed, float* z, int32_t* comp, svae_stream_t stream);
 
+/* ---- ELBO surgery of the latents: the density of the aggregate posterior q(z) = (1 / N) sum_j q(z | x_j) against all
+ * N rows of the index, and the split of the mean KL built on it (csrc/aggpost.hip; the corpus-level form of marginal_kl,
+ * math_utils.py:51-58, which estimates the split inside one batch and so cannot exceed log B) ------------------------------
+ * Row j of the index is N(loc_j, diag(scale_j^2)). For a point z_i:
+ *   l_ijd    = -1/2 ((z_id - loc_jd) / scale_jd)^2 - log scale_jd - 1/2 log 2 pi,      l_ij = sum_d l_ijd
+ *   logq_i   = logsumexp_{j not skip_i} l_ij  - log n_i
+ *   logq_dim = logsumexp_{j not skip_i} l_ijd - log n_i                                 (one per dimension d)
+ * with n_i = N, or N - 1 where skip_i names a row (leave-one-out: the point's own component is left out).
+ * z is f32 [M][Z], loc and scale f32 [N][Z], all 16-byte aligned; Z a multiple of 4 in 4..256; 1 <= M, N <= 2^24; with a
+ * non-NULL skip N >= 2. Every entry point returns 1 before any launch on a NULL required operand, a misaligned pointer,
+ * a shape out of range or a workspace that is too small; the *_ws_bytes companions return 0 on a bad shape. ws:
+ * caller-owned, 16-byte aligned, contents need not survive. Nothing below uses an atomic: grids and orders depend on
+ * (M, N, Z) alone, so two calls on one input agree bit for bit. Operands must be finite, scale > 0, and every
+ * |(z - loc) / scale| below 2^63, so that every term is a finite f32.
+ * svae_aggpost_logq: skip int32 [M] or NULL: the row each point leaves out; -1, or any value outside 0..N-1, leaves
+ *   none out. logq f32 [M]; logq_dim f32 [M][Z] or NULL (then no per-dimension work is done: it is another kernel).
+ *   A workgroup owns SVAE_AGGPOST_POINTS_PER_BLOCK points (one per lane, in registers) and one slice of consecutive
+ *   rows; the rows are cut into slices (svae_aggpost_geometry: from (M, N) alone) so that a small M still fills the
+ *   chip. It streams its slice through LDS in tiles of SVAE_AGGPOST_TILE_ROWS rows, staging per element loc, the
+ *   multiplier w = 1.f / scale (one rounding) and logf(scale) (1 ulp), computed once per tile on load.
+ *   Terms, in f32 from direct differences (no |z|^2 - 2 z.loc + |loc|^2 expansion), d = z - loc, t = d * w:
+ *     joint    q from two fmaf chains acc = fmaf(t, t, acc) over elements 0, 2 and elements 1, 3 of the float4 chunks in
+ *              chunk order, q their sum; c_j = (float)(-(sum_d (double)logf(scale_jd)) - Z / 2 log 2 pi), the sum in f64;
+ *              l_ij = fmaf(-0.5, q, c_j).
+ *              |error| <= ((Z / 2 + 7) q / 2 + 2 sum_d |log scale_jd| + |c_j| + |l_ij|) 2^-24 to first order.
+ *     per dim  l_ijd = fmaf(-0.5f * t, t, nc), nc = -(logf(scale) + 0.9189385f) in f32.
+ *              |error| <= (3 t^2 + 3 |log scale| + 1.84 + |l_ijd|) 2^-24 to first order.
+ *   Accumulation, per output and slice: a running maximum Mx (f32, from the finite floor -1e38, so the loop forms
+ *   neither NaN nor -inf) and a carried sum S (f64, from 0). Per tile s (f32) = 0 and M0 = Mx; per row in ascending
+ *   order Mn = max(Mx, l), s = fmaf(s, ex(Mx - Mn), ex(l - Mn)), Mx = Mn, with ex(x) = v_exp_f32(x * 1.442695f) (one of
+ *   the two arguments is 0 and ex(0) is exactly 1); a skipped row leaves Mx alone and adds 0. After the tile S = S + s
+ *   where Mx == M0, else S = S * exp((double)M0 - (double)Mx) + s in f64. An f32 sum therefore spans at most
+ *   SVAE_AGGPOST_TILE_ROWS terms and everything carried further is f64: relative to the true sum of the device's own
+ *   terms, S is off by at most [sum_j r_j (3 |l_j - max| + 2) + T (3 + 3 max(1, ln T))] 2^-24 with r the terms' shares
+ *   and T the tile rows, whatever N is. Each (point block, slice) workgroup leaves the partial (Mx, S) per point, and
+ *   the per-dimension kernel (grid: point blocks x slices x dimension passes of SVAE_AGGPOST_PASS_DIMS dimensions, so a
+ *   lane holds its point, the maxima and the f64 sums of one pass in registers whatever Z is) one per (point,
+ *   dimension); a slice whose rows are all skipped leaves (-inf, 0). A second kernel merges the slices in ascending
+ *   order in f64: Mt = max_s Mx_s, St = sum_s S_s exp(Mx_s - Mt) over the slices that are not (-inf, 0) (-inf - (-inf)
+ *   is never formed), output (float)(Mt + log St - log n_i), rounded once.
+ *   ws >= svae_aggpost_ws_bytes = slices * M * (per_dim ? 1 + Z : 1) * 16 bytes, slices = ceil(N / rows per slice),
+ *   rows per slice = max(64, ceil(N / ceil(1024 / point blocks))) rounded up to the tile rows (one slice from 1024
+ *   point blocks on): slices * M stays below 1024 * 256 + M + 256.
+ * svae_aggpost_decompose: src int32 [M]: the row of (loc, scale) each point was drawn from (0 <= src_i < N is the
+ *   caller's to guarantee: the entry point does not know N); logq, logq_dim as above, both required.
+ *   out f64 [4 + Z] = {mi, marginal_kl, tc, kl_mc, dim_kl[Z]} with, for p = N(0, I),
+ *     mi = mean_i(log q(z_i | x_src_i) - logq_i),       marginal_kl = mean_i(logq_i - log p(z_i)),
+ *     tc = mean_i(logq_i - sum_d logq_dim_id),          dim_kl_d = mean_i(logq_dim_id - log p(z_id)),
+ *   kl_mc = mi + marginal_kl; marginal_kl = tc + sum_d dim_kl_d to f64 rounding. Every term is formed in f64 from the
+ *   f32 operands (sums over d in ascending d). The means are f64 sums in a fixed order, as svae_mmd_rowterm's: B =
+ *   min(ceil(M / 256), 1024) workgroups; thread t of workgroup b adds its points b 256 + t + k B 256 in ascending k, a
+ *   64-lane xor butterfly, the four waves in order; for dim_kl thread d adds the workgroup's points in ascending
+ *   order; one workgroup then adds the B partials in ascending order and divides by M.
+ *   ws >= svae_aggpost_decompose_ws_bytes = B * (3 + Z) * 8 bytes.
+ * svae_aggpost_geometry: geom (HOST int32 [6]) = {points per workgroup, point blocks, row slices, rows per slice, tile
+ *   rows, dimensions held per pass (per_dim: min(Z, SVAE_AGGPOST_PASS_DIMS); else Z, the joint kernel holds the whole
+ *   point)}. */
+#define SVAE_AGGPOST_POINTS_PER_BLOCK 256
+#define SVAE_AGGPOST_TILE_ROWS 16
+#define SVAE_AGGPOST_PASS_DIMS 16
+int svae_aggpost_geometry(int32_t M, int32_t N, int32_t Z, int32_t per_dim, int32_t* geom);
+int64_t svae_aggpost_ws_bytes(int32_t M, int32_t N, int32_t Z, int32_t per_dim);
+int svae_aggpost_logq(const float* z, int32_t M, const float* loc, const float* scale, int32_t N, int32_t Z,
+                      const int32_t* skip, float* logq, float* logq_dim, void* ws, int64_t ws_bytes,
+                      svae_stream_t stream);
+int64_t svae_aggpost_decompose_ws_bytes(int32_t M, int32_t Z);
+int svae_aggpost_decompose(const float* z, const int32_t* src, const float* loc, const float* scale, const float* logq,
+                           const float* logq_dim, int32_t M, int32_t Z, void* ws, int64_t ws_bytes, double* out,
+                           svae_stream_t stream);
+
 /* ---- reconstruction scoring over token ids: the integer counts behind BLEU, token accuracy and the edit rate of P
  * (candidate, reference) pairs (csrc/textscore.hip; what stands in for reconstruction_bleu of math_utils.py:9-38, whose
  * keys past its second order are not n-grams) --------------------------------------------------------------------------

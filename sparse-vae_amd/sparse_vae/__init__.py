@@ -9,6 +9,7 @@ from .latent_index import LatentIndex, gather_latents  # noqa: F401
 from .tsne import TSNE  # noqa: F401
 from .kmeans import KMeans  # noqa: F401
 from .mixture import GaussianMixture  # noqa: F401
+from .surgery import ElboSurgery  # noqa: F401
 from .reconstruction import (ReconstructionScores, interpolate_latents, reference_rows,  # noqa: F401
                              score_reconstructions)
 from .batch_generation import batch_generate_samples, trim_samples  # noqa: F401

@@ -30,6 +30,8 @@ PAIRSUM_TILE_COLS, PAIRSUM_MAX_P, MMD_REDUCE_BLOCKS = 32, 8, 256   # SVAE_PAIRSU
 KMEANS_MAX_K, KMEANS_TILE_CENTROIDS, KMEANS_SORT_BLOCKS, KMEANS_SEED_BLOCK_ROWS = 1024, 32, 256, 256
 # SVAE_GMM_MAX_K, _TILE_COMPONENTS, _ROWS_PER_BLOCK
 GMM_MAX_K, GMM_TILE_COMPONENTS, GMM_ROWS_PER_BLOCK = 256, 16, 256
+# SVAE_AGGPOST_POINTS_PER_BLOCK, _TILE_ROWS, _PASS_DIMS
+AGGPOST_POINTS_PER_BLOCK, AGGPOST_TILE_ROWS, AGGPOST_PASS_DIMS = 256, 16, 16
 TEXT_MAX_LEN = 2048                                  # SVAE_TEXT_MAX_LEN
 BEAM_MAX_W = 16                                      # SVAE_BEAM_MAX_W
 
@@ -251,6 +253,13 @@ _SIGS = {
                        c_void_p, c_int64, c_void_p],
     'svae_gmm_sample': [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
                         c_void_p],
+    'svae_aggpost_geometry': [c_int32, c_int32, c_int32, c_int32, c_void_p],
+    'svae_aggpost_ws_bytes': [c_int32, c_int32, c_int32, c_int32],
+    'svae_aggpost_logq': [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                          c_void_p, c_int64, c_void_p],
+    'svae_aggpost_decompose_ws_bytes': [c_int32, c_int32],
+    'svae_aggpost_decompose': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
+                               c_int64, c_void_p, c_void_p],
     'svae_ngram_overlap': [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p],
     'svae_edit_distance': [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p],
     'svae_version': [],
@@ -275,6 +284,7 @@ def _load():
                       'svae_kmeans_seed_ws_bytes': c_int64,
                       'svae_gmm_params_floats': c_int64, 'svae_gmm_estep_ws_bytes': c_int64,
                       'svae_gmm_mstep_ws_bytes': c_int64,
+                      'svae_aggpost_ws_bytes': c_int64, 'svae_aggpost_decompose_ws_bytes': c_int64,
                       'svae_gemm_group_table_bytes': c_int64}.get(name, ctypes.c_int)
     return lib
 

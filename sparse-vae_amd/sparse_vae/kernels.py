@@ -1433,3 +1433,70 @@ def gmm_sample(params, K, Z, n, seed=0, u=None, eps=None):
     check(lib.svae_gmm_sample(params.data_ptr(), K, Z, n, ptr(u), ptr(eps), int(seed) & (2 ** 64 - 1), z.data_ptr(),
                               comp.data_ptr(), stream()), 'svae_gmm_sample')
     return z, comp
+
+
+def aggpost_geometry(m, n, Z, per_dim=False):
+    """svae_aggpost_geometry: (points per workgroup, point blocks, row slices, rows per slice, tile rows, dimensions
+    held per pass)."""
+    geom = (ctypes.c_int32 * 6)()
+    check(lib.svae_aggpost_geometry(m, n, Z, int(bool(per_dim)), ctypes.addressof(geom)), 'svae_aggpost_geometry')
+    return tuple(geom)
+
+
+def _aggpost_shape(z, loc, scale, name):
+    m, Z = _mmd_rows(z, f'{name} z')
+    n, Zr = _mmd_rows(loc, f'{name} loc')
+    _latent_rows(loc, scale)
+    if Zr != Z:
+        raise ValueError(f'{name}: the points have {Z} dimensions and the rows {Zr}')
+    return m, n, Z
+
+
+def aggpost_logq(z, loc, scale, skip=None, per_dim=False, logq=None, logq_dim=None):
+    """svae_aggpost_logq: the log-density of the aggregate posterior (1 / N) sum_j N(loc_j, scale_j^2) at the points
+    z f32 [M, Z] against the rows loc, scale f32 [N, Z] -> logq f32 [M], or with per_dim (logq, logq_dim f32 [M, Z],
+    the same per latent dimension). skip int32 [M] or None: the row each point leaves out (-1: none; needs N >= 2).
+    The workspace is allocated per call (stream-ordered by the caching allocator)."""
+    m, n, Z = _aggpost_shape(z, loc, scale, 'aggpost_logq')
+    dev = z.device
+    if skip is not None:
+        _kmeans_vec(skip, torch.int32, m, 'skip')
+        if n < 2:
+            raise ValueError('aggpost_logq: leaving a row out needs at least two rows')
+    logq = torch.empty(m, dtype=f32, device=dev) if logq is None else logq
+    _kmeans_vec(logq, f32, m, 'logq')
+    if logq_dim is None and per_dim:
+        logq_dim = torch.empty(m, Z, dtype=f32, device=dev)
+    if logq_dim is not None:
+        _kmeans_vec(logq_dim, f32, m * Z, 'logq_dim')
+    nbytes = lib.svae_aggpost_ws_bytes(m, n, Z, int(logq_dim is not None))
+    ws = torch.empty(nbytes // 16, 2, dtype=torch.float64, device=dev)
+    check(lib.svae_aggpost_logq(z.data_ptr(), m, loc.data_ptr(), scale.data_ptr(), n, Z, ptr(skip), logq.data_ptr(),
+                                ptr(logq_dim), ws.data_ptr(), nbytes, stream()), 'svae_aggpost_logq')
+    return (logq, logq_dim) if logq_dim is not None else logq
+
+
+def aggpost_decompose(z, src, loc, scale, logq, logq_dim, out=None):
+    """svae_aggpost_decompose: out f64 [4 + Z] = (mi, marginal_kl, tc, kl_mc, dim_kl[Z]) of the points z f32 [M, Z]
+    drawn from the rows src int [M] of loc, scale f32 [N, Z], from their logq f32 [M] and logq_dim f32 [M, Z]. A CPU
+    src outside 0..N-1 raises IndexError; a device src is not read back, its rows are clamped into that range."""
+    m, n, Z = _aggpost_shape(z, loc, scale, 'aggpost_decompose')
+    dev = z.device
+    if not torch.is_tensor(src) or src.is_floating_point() or src.numel() != m:
+        raise ValueError(f'aggpost_decompose: src must hold {m} integer rows')
+    if src.is_cuda:
+        src = src.reshape(-1).clamp(0, n - 1).to(torch.int32).contiguous()
+    else:
+        if not (0 <= int(src.min()) and int(src.max()) < n):
+            raise IndexError(f'aggpost_decompose: src outside the rows (0..{n - 1})')
+        src = src.reshape(-1).to(dev, torch.int32).contiguous()
+    _kmeans_vec(logq, f32, m, 'logq')
+    _kmeans_vec(logq_dim, f32, m * Z, 'logq_dim')
+    out = torch.empty(4 + Z, dtype=torch.float64, device=dev) if out is None else out
+    _kmeans_vec(out, torch.float64, 4 + Z, 'out')
+    nbytes = lib.svae_aggpost_decompose_ws_bytes(m, Z)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    check(lib.svae_aggpost_decompose(z.data_ptr(), src.data_ptr(), loc.data_ptr(), scale.data_ptr(), logq.data_ptr(),
+                                     logq_dim.data_ptr(), m, Z, ws.data_ptr(), nbytes, out.data_ptr(), stream()),
+          'svae_aggpost_decompose')
+    return out

@@ -250,6 +250,32 @@ class LatentIndex:
             return gm.fit(self)          # the empty and the CPU index are refused there
         return gm.fit(self.loc.contiguous())
 
+    def log_density(self, z, per_dim: bool = False, skip=None):
+        """log q(z) of the aggregate posterior q(z) = (1 / N) sum_j N(loc_j, scale_j^2) at the points z [M, Z], against
+        every row of the index (svae_aggpost_logq): logq f32 [M] on the device, or with per_dim (logq, logq_dim f32
+        [M, Z], the log-density of each dimension's marginal). skip: int [M], the row each point leaves out of the sum
+        (-1: none), e.g. the row it was drawn from; the density is then over the N - 1 others."""
+        loc, _, _, _ = self._corpus()
+        z = _rows(torch.as_tensor(z), self.latent_depth, 'z').to(self._device).contiguous()
+        if skip is not None:
+            skip = torch.as_tensor(skip).reshape(-1).to(self._device, torch.int32).contiguous()
+            if skip.numel() != z.shape[0]:
+                raise ValueError(f'log_density: {skip.numel()} skip rows for {z.shape[0]} points')
+        return K.aggpost_logq(z, loc, self._scale[:self._n], skip=skip, per_dim=per_dim)
+
+    def elbo_surgery(self, samples: Optional[int] = None, seed: int = 0, leave_one_out: bool = False, eps=None,
+                     rows=None):
+        """The mean KL of the index split as I_q(x; z) + KL(q(z) || p(z)), and the marginal term as a total correlation
+        plus per-dimension KLs: an ElboSurgery (sparse_vae.surgery, which says what each field is and which way each
+        variant is biased). One z_i ~ q(z | x_i) is drawn per sampled row (svae_latent_draw keyed by `seed`, or
+        loc + scale * eps with eps f32 [samples, Z] injected) and log q(z_i) is taken against all N rows. rows: the
+        rows to draw from; default all of them when samples is None or >= N, else a sorted subset from a seeded
+        torch.randperm on the CPU. leave_one_out: leave each point's own row out of q(z_i)."""
+        from .surgery import elbo_surgery
+        loc, _, _, _ = self._corpus()
+        return elbo_surgery(loc, self._scale[:self._n], samples=samples, seed=seed, leave_one_out=leave_one_out,
+                            eps=eps, rows=rows)
+
     # ------------------------------------------------------------------ persistence
     def save(self, path):
         """One .npz: loc, scale, titles. The derived rows are not stored (load recomputes them)."""
